@@ -18,6 +18,12 @@ leg (every rank prunes its own model, no collective: weak scaling) is reported b
 --config cfg5 (BASELINE configs[4]): 64 blocks of 4096^2 (db8 level 5) split over the ranks
 (strong scaling); --config cfg3 the MLP (launch-latency regime).
 
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last one when
+--dump-outputs is given, and prints the result line.  --full adds every other leg to that line: the
+rocprofv3 kernel-stats child, a separate replay distribution, the dominant kernel's launch span and
+roofline, the cold Infinity Cache legs, the N > 1 compute / exchange / replica legs and the CPU
+baseline (each still switched off by its own --no-* option).
+
 Prints ONE JSON line on rank 0 (the driver contract).
 """
 import argparse
@@ -48,6 +54,9 @@ KERNEL_OF_STAGE = {"k_window": "k_window", "k_collect": "k_collect_t", "k_mask_s
                    "forward_dwt": "k_fwd_int+k_fwd_level", "inverse_dwt": "k_inv_int+k_inv_level"}
 DWT_STAGES = ("forward_dwt", "inverse_dwt")
 CFG5_BLOCKS = 64
+# untimed graph replays enqueued directly in front of the timed ones: LEAD_IN_MS of device time,
+# at least 2 and at most 60 replays (what the per-replay distribution used to run)
+LEAD_IN_MS, LEAD_IN_MIN, LEAD_IN_MAX = 20.0, 2, 60
 DB8_L5_FLOP_PER_ELEM = 170.5  # 4 F sum_k 4^-k MACs, no FMA, F = 16, L = 5
 
 
@@ -57,9 +66,17 @@ def parse():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="cfg2", choices=["cfg2", "cfg3", "cfg5"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg (rocprofv3 child, replay distribution, launch "
+                         "spans / stage intervals and roofline, cold Infinity Cache, N > 1 legs, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0): out_NNN.npy the pruned "
+                         "tensors (float32; a fixed seeded sample of each when they exceed 60 MB in all), records.npy "
+                         "one float64 row per tensor (RECORD_COLUMNS)")
     ap.add_argument("--blocks", type=int, default=CFG5_BLOCKS, help="cfg5: 4096^2 blocks in all (split over ranks)")
     ap.add_argument("--graph-steps", type=int, default=10, help="steps captured per hipGraph replay")
-    ap.add_argument("--replays", type=int, default=60, help="graph replays timed one by one (p10/p50/p90)")
+    ap.add_argument("--replays", type=int, default=60,
+                    help="--full: graph replays timed one by one after the headline (replay_distribution_ms)")
     ap.add_argument("--stamp-reps", type=int, default=50, help="launches timed by in-kernel stamps")
     ap.add_argument("--stage-reps", type=int, default=20,
                     help="calls timed stage by stage (0: no stage leg and no roofline object; tools/pmc_run.sh)")
@@ -190,7 +207,7 @@ def child_steps(args):
     graph (when one is captured), then the timed steps."""
     K = max(args.steps, 200)
     G = max(1, min(args.graph_steps, K))
-    return args.warmup + K + (0 if args.no_graph else 1 + 2 * G)
+    return max(1, args.warmup) + K + (0 if args.no_graph else 1 + 2 * G)
 
 
 def dwt_stage_work(shapes_levels, F):
@@ -214,6 +231,35 @@ def dwt_stage_work(shapes_levels, F):
             inv += 4 * B * (4 * R[k] * C[k] + (H * W if k == 1 else 4 * R[k] * C[k]))
             flops += 2 * 8 * F * R[k] * C[k] * B  # per stage
     return {"forward_dwt": fwd, "inverse_dwt": inv, "flops_per_stage": flops}
+
+
+RECORD_COLUMNS = ["numel", "zero_count", "coeff_numel", "thr64", "thr32", "max_abs", "eff_level", "path"]
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # the out_NNN.npy files in all
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, tensors, recs):
+    """DIR/out_NNN.npy: pruned tensor NNN as float32, whole when all of them fit DUMP_BUDGET_BYTES,
+    otherwise the elements at a fixed sample of flat positions (the same count for every tensor,
+    drawn from DUMP_SEED + NNN, ascending).  DIR/records.npy: float64 [tensors, RECORD_COLUMNS]."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    whole = 4 * sum(t.numel() for t in tensors) <= DUMP_BUDGET_BYTES
+    per = DUMP_BUDGET_BYTES // 4 // max(1, len(tensors))
+    for i, t in enumerate(tensors):
+        flat = t.detach().reshape(-1)
+        if not whole and flat.numel() > per:
+            idx = np.sort(np.random.default_rng(DUMP_SEED + i).integers(0, flat.numel(), size=per))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            a = flat.cpu().numpy()
+        else:
+            a = flat.cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(dirname, "out_%03d.npy" % i), a.astype(np.float32, copy=False))
+    rows = np.zeros((len(recs), len(RECORD_COLUMNS)), np.float64)
+    for i, r in enumerate(recs):
+        f32 = np.array([r["thr32_bits"], r["max_abs_bits"]], np.uint32).view(np.float32)
+        rows[i] = [r["numel"], r["zero_count"], r["coeff_numel"], r["thr64"], f32[0], f32[1], r["eff_level"], r["path"]]
+    np.save(os.path.join(dirname, "records.npy"), rows)
 
 
 def cpu_model():
@@ -242,7 +288,8 @@ def main():
     # single process: first the kernel-stats child (rocprofv3 over this same step loop), before
     # this process touches the GPU; its per-kernel average is the roofline's launch duration
     prof_stats = None
-    if (not args.profile_child and not args.no_rocprof and int(os.environ.get("WORLD_SIZE", "1")) == 1):
+    if (args.full and not args.profile_child and not args.no_rocprof
+            and int(os.environ.get("WORLD_SIZE", "1")) == 1):
         prof_stats = rocprof_child(args)
 
     import torch
@@ -378,9 +425,14 @@ def main():
         if diag:
             with open("/proc/self/maps") as fi, open(os.path.join(diag, "maps.txt"), "w") as fo:
                 fo.write(fi.read())
+        warm = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        warm[0].record()
         for _ in range(2):
             graph.replay()
+        warm[1].record()
         torch.cuda.synchronize()
+        warm_ms = max(warm[0].elapsed_time(warm[1]) / 2, 1e-3)  # one replay
+        lead_in = int(min(LEAD_IN_MAX, max(LEAD_IN_MIN, LEAD_IN_MS // warm_ms + 1)))
 
     def max_over_ranks(t):
         if world == 1:
@@ -417,21 +469,71 @@ def main():
         return int(engine.fault_mask(res_buf, len(xs)).sum()) if xs else 0
 
     # ------------------------------------------------------------ the headline
+    # exactly K = --steps steps are timed.  Without a graph: between barrier + synchronize, max over
+    # ranks.  With one: K // G replays of G steps, bracketed by HIP events on the replay stream in
+    # at most 1000 intervals, then the K % G steps left over, eager; value and ms_per_step are the
+    # p50 over the intervals, so a short --steps does not hinge on the launch latency of the first
+    # replay.  lead_in untimed replays (LEAD_IN_MS of device time by the two warm replays' own
+    # duration) go directly in front, with no wait in between: the host enqueues ahead of the
+    # device, and the device is past its first milliseconds of work after an idle spell (measured
+    # 1 to 3 % slower, cfg2) when the first interval starts.  The rocprofv3 child times
+    # nothing: it runs its K steps without lead-in or events (event-bracketed replays of cfg5 have
+    # crashed inside the profiler, profiles/r03_cfg5_rocprofv3_sigsegv.txt).
     K = args.steps
-    T = timed(K)  # exactly K steps between barrier + synchronize, max over ranks
-    ms_per_step = T / K * 1e3
-    value = n_model * K / T
-    timed_region = {"steps": K, "ms_per_step": ms_per_step, "value": value}
+    dist_ms = None
+    if graph is None or args.profile_child:
+        T = timed(K)
+        ms_per_step = T / K * 1e3
+        value = n_model * K / T
+        timed_region = {"steps": K, "ms_per_step": ms_per_step, "value": value}
+        value_src = "the K-step timed region (barrier + synchronize on both sides, max over ranks)"
+    else:
+        nrep = K // G
+        chunk = -(-nrep // 1000)
+        ivs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), min(chunk, nrep - i))
+               for i in range(0, nrep, chunk)]
+        first, last = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        for _ in range(lead_in):
+            graph.replay()
+        first.record()
+        for a, b, n in ivs:
+            a.record()
+            for _ in range(n):
+                graph.replay()
+            b.record()
+        for _ in range(K % G):
+            step()
+        last.record()
+        torch.cuda.synchronize()
+        per = np.array([a.elapsed_time(b) / (n * G) for a, b, n in ivs])
+        dist_ms = {"replays": nrep, "steps_per_replay": G, "intervals": len(ivs), "lead_in_replays": lead_in,
+                   "p10": float(np.percentile(per, 10)), "p50": float(np.percentile(per, 50)),
+                   "p90": float(np.percentile(per, 90))}
+        ms_per_step = dist_ms["p50"]
+        value = n_model / (ms_per_step * 1e-3)
+        span = first.elapsed_time(last)
+        timed_region = {"steps": K, "ms_per_step": span / K, "value": n_model * K / (span * 1e-3)}
+        value_src = ("p50 over the %d graph replays of %d steps each that make up the K timed steps (%d intervals "
+                     "between HIP events on the replay stream); the whole K-step span, first event to last, "
+                     "is reported beside it as timed_region" % (nrep, G, len(ivs)))
     if args.profile_child:
         return
     faults_timed = faulted_now()
 
-    # per-replay distribution (>= 50 replays of G steps, each bracketed by events on the stream);
-    # with a graph the headline value and ms_per_step are its p50, so that a short --steps (the
-    # driver's 20 = 2 replays) cannot hinge on one or two replays
-    dist_ms = None
-    value_src = "the K-step timed region (barrier + synchronize on both sides, max over ranks)"
-    if graph is not None:
+    if args.dump_outputs and rank == 0:
+        if sharded:
+            dump_t, dump_r = assemble(shard.full, plan)
+        else:
+            dump_t = outs
+            dump_r = [{k: r[k].item() for k in engine.RESULT_DTYPE.names}
+                      for r in res_buf.cpu().numpy().view(engine.RESULT_DTYPE)[:len(xs)]]
+        dump_outputs(args.dump_outputs, dump_t, dump_r)
+
+    # --full: a distribution over replays of their own (>= 50 replays of G steps, each bracketed by
+    # events on the stream), beside the headline's
+    replay_ms = None
+    if graph is not None and args.full:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                for _ in range(max(50, args.replays))]
         for a, b in evs:
@@ -440,13 +542,9 @@ def main():
             b.record()
         torch.cuda.synchronize()
         per = np.array([a.elapsed_time(b) / G for a, b in evs])
-        dist_ms = {"replays": len(evs), "steps_per_replay": G, "p10": float(np.percentile(per, 10)),
-                   "p50": float(np.percentile(per, 50)), "p90": float(np.percentile(per, 90))}
-        ms_per_step = dist_ms["p50"]
-        value = n_model / (ms_per_step * 1e-3)
-        value_src = ("p50 of %d graph replays of %d steps each, HIP events on the replay stream; the K-step timed "
-                     "region is reported beside it as timed_region" % (len(evs), G))
-    faults_timed += faulted_now()
+        replay_ms = {"replays": len(evs), "steps_per_replay": G, "p10": float(np.percentile(per, 10)),
+                     "p50": float(np.percentile(per, 50)), "p90": float(np.percentile(per, 90))}
+        faults_timed += faulted_now()
 
     # ------------------------------------- dominant kernel: in-kernel launch span
     def stamp_spans(reps, before=None):
@@ -469,7 +567,7 @@ def main():
 
     stage_us, dom, dom_us, dom_bytes, dom_launches, timing_src = {}, None, None, 0, 1, None
     work = None
-    if (resident or small) and xs:
+    if args.full and (resident or small) and xs:
         # one launch per step: its algorithmic bytes are every weight read once and written once
         spans = stamp_spans(args.stamp_reps)
         dom = "k_resident" if resident else "k_small"
@@ -477,7 +575,7 @@ def main():
         timing_src = ("in-kernel s_memrealtime stamps: first workgroup start -> last workgroup end after its "
                       "stores completed, mean of %d back-to-back launches (wtp_set_kernel_stamps)" % len(spans))
         stage_us = {dom: dom_us}
-    elif xs and args.stage_reps > 0:
+    elif args.full and xs and args.stage_reps > 0:
         # stage intervals from HIP events the library records between its launches (include dispatch
         # gaps); a spin kernel in front lets the whole call be enqueued before it runs
         sevs = [torch.cuda.Event(enable_timing=True) for _ in range(len(STAGES) + 1)]
@@ -542,7 +640,7 @@ def main():
     # writes one of them back to HBM); "read" -- a 512 MiB read of another buffer, which leaves it
     # full of clean lines (the step's data comes from HBM, nothing else is written back)
     cold = None
-    if not args.no_cold and not sharded and xs:
+    if args.full and not args.no_cold and not sharded and xs:
         flush = torch.empty(512 << 20 >> 2, dtype=torch.float32, device=dev)
         flush.fill_(1.0)
         cold = {}
@@ -574,7 +672,7 @@ def main():
 
     # ------------------------------------------------- N > 1 legs (cfg4 split, replicas)
     multi = None
-    if sharded:
+    if sharded and args.full:
         Kc = max(20, K // 4)
         t_comp = timed(Kc, compute) / Kc * 1e3
         t_gath = timed(Kc, gather) / Kc * 1e3
@@ -616,7 +714,7 @@ def main():
 
     # --------------------------------------------- CPU baseline (rank 0, N = 1 only)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import oracle as O
         host = [O.synth(s, seed, tid, e) for (s, seed, tid, e) in mine]
         if args.config == "cfg5":
@@ -652,7 +750,7 @@ def main():
     if rank == 0:
         line = {
             "metric": METRIC, "value": value, "unit": "weight-coeffs/s", "n_gpus": world, "steps": K,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+            "warmup": args.warmup, "full": args.full, "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": "strong" if world > 1 else "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic (splitmix64 Irwin-Hall, kaiming-scaled)",
             "config": {"workload": name, "config": args.config if not sharded else "cfg4",
@@ -673,6 +771,7 @@ def main():
             "timed_region": timed_region,
             "pipeline_hbm_gbs": 8 * n_model / (ms_per_step * 1e-3) / 1e9,
             "step_distribution_ms": dist_ms,
+            "replay_distribution_ms": replay_ms,
             "roofline": None if dom is None else {
                 "bound": "hbm", "kernel": dom_kernel, "stage": dom, "launches_per_stage": dom_launches,
                 "achieved": dom_bytes / (dom_us * 1e-6) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",

@@ -22,7 +22,7 @@ for c in $CFGS; do
   for v in new base new base; do
     L=${NEW_LIB:-}; [ $v = base ] && L=${BASE_LIB:-$(pwd)/tools/ab/libwtprune_base.so}
     NC="--no-cold"; [ -n "$COLD" ] && NC=""
-    WTP_LIB_PATH=$L timeout -k 10 300 python bench.py --config $c --no-cpu $NC $X > $OUT/b_${TAG}_${c}_$v.log 2>&1 || { tail -20 $OUT/b_${TAG}_${c}_$v.log; exit 1; }
+    WTP_LIB_PATH=$L timeout -k 10 300 python bench.py --full --config $c --no-cpu $NC $X > $OUT/b_${TAG}_${c}_$v.log 2>&1 || { tail -20 $OUT/b_${TAG}_${c}_$v.log; exit 1; }
     python3 -c "
 import json
 d=json.loads([l for l in open('$OUT/b_${TAG}_${c}_$v.log') if l.startswith('{')][-1]); r=d['roofline']

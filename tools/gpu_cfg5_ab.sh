@@ -11,7 +11,7 @@ for rep in 1 2; do
   i=0
   for v in "$@"; do
     i=$((i+1))
-    timeout -k 10 400 python bench.py --config cfg5 --steps 10 --warmup 2 --replays 10 --no-cpu --no-cold $v > $OUT/c5_${TAG}_$i.log 2>&1 || { tail -20 $OUT/c5_${TAG}_$i.log; exit 1; }
+    timeout -k 10 400 python bench.py --full --config cfg5 --steps 10 --warmup 2 --replays 10 --no-cpu --no-cold $v > $OUT/c5_${TAG}_$i.log 2>&1 || { tail -20 $OUT/c5_${TAG}_$i.log; exit 1; }
     python3 -c "
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r=d['roofline']

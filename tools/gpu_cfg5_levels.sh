@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$ROOT"; mkdir -p gpurun_out
 i=0
 for v in "$@"; do
   d=gpurun_out/lv_${TAG}_$i
-  WTP_BENCH_TRACE_DIR=$d timeout -k 10 400 python bench.py --config cfg5 --steps 10 --warmup 2 --no-cpu --no-cold \
+  WTP_BENCH_TRACE_DIR=$d timeout -k 10 400 python bench.py --full --config cfg5 --steps 10 --warmup 2 --no-cpu --no-cold \
     --no-graph --pipeline 0 $v > $d.log 2>&1 || { tail -5 $d.log; exit 1; }
   echo "== variant '$v'"
   python3 - $d.log <<'PY' || exit 1

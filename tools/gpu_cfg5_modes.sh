@@ -24,6 +24,7 @@ if [ "${TRACE:-0}" = 1 ]; then
   for form in graph eager; do
     X=""; [ $form = eager ] && X="--no-graph"
     WTP_BENCH_TRACE_DIR=gpurun_out/trace_${form}_$TAG timeout -k 10 400 python bench.py --config cfg5 --steps 10 \
+      --full \
       --warmup 2 --replays 10 --no-cpu --no-cold $X > gpurun_out/c5_t${form}_$TAG.log 2>&1 \
       || { tail -5 gpurun_out/c5_t${form}_$TAG.log; exit 1; }
     grep -c Fill gpurun_out/trace_${form}_$TAG/run_kernel_trace.csv || true

@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 "$OUT/gpu_$TAG.log"
 fi
 echo "== bench cfg5"
-timeout -k 10 500 python bench.py --config cfg5 --steps 20 --warmup 3 --no-cpu --no-cold > "$OUT/bench_cfg5_$TAG.log" 2>&1 || { echo bench failed; tail -30 "$OUT/bench_cfg5_$TAG.log"; exit 1; }
+timeout -k 10 500 python bench.py --full --config cfg5 --steps 20 --warmup 3 --no-cpu --no-cold > "$OUT/bench_cfg5_$TAG.log" 2>&1 || { echo bench failed; tail -30 "$OUT/bench_cfg5_$TAG.log"; exit 1; }
 tail -1 "$OUT/bench_cfg5_$TAG.log" | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']

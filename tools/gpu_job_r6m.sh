@@ -12,7 +12,7 @@ bash tools/gpu_cfg5_levels.sh m "" "--no-fused-select" > $OUT/levels.txt 2>&1 ||
 grep -E "variant|ms/step|k_fwin|k_fslot|k_collect|k_window|k_mask|k_fwd_int<16, false>" $OUT/levels.txt
 for v in fused unfused fused unfused; do
   X=""; [ $v = unfused ] && X="--no-fused-select"
-  timeout -k 10 300 python bench.py --config cfg5 --no-cpu --no-cold --steps 10 --warmup 2 --replays 10 $X > $OUT/b_$v.log 2>&1 || { tail -20 $OUT/b_$v.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --config cfg5 --no-cpu --no-cold --steps 10 --warmup 2 --replays 10 $X > $OUT/b_$v.log 2>&1 || { tail -20 $OUT/b_$v.log; exit 1; }
   python3 -c "
 import json
 d=json.loads([l for l in open('$OUT/b_$v.log') if l.startswith('{')][-1]); r=d['roofline']

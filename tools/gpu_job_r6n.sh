@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_fused_select.py tests/test_
 tail -1 $OUT/t.log
 for v in fused unfused fused unfused; do
   X=""; [ $v = unfused ] && X="--no-fused-select"
-  timeout -k 10 300 python bench.py --config cfg5 --no-cpu --no-cold --steps 10 --warmup 2 --replays 10 $X > $OUT/b_$v.log 2>&1 || { tail -20 $OUT/b_$v.log; exit 1; }
+  timeout -k 10 300 python bench.py --full --config cfg5 --no-cpu --no-cold --steps 10 --warmup 2 --replays 10 $X > $OUT/b_$v.log 2>&1 || { tail -20 $OUT/b_$v.log; exit 1; }
   python3 -c "
 import json
 d=json.loads([l for l in open('$OUT/b_$v.log') if l.startswith('{')][-1]); r=d['roofline']

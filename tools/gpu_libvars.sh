@@ -14,7 +14,7 @@ X=""; [ $CFG = cfg5 ] && X="--steps 10 --warmup 2 --replays 10"
 for r in $(seq 1 ${ROUNDS:-2}); do
   for v in ${VARIANTS:-cur}; do
     L=""; [ $v != cur ] && L=$(pwd)/tools/ab/libwtprune_$v.so
-    WTP_LIB_PATH=$L timeout -k 10 300 python bench.py --config $CFG --no-cpu ${COLD:---no-cold} $X > $OUT/b_${v}_$r.log 2>&1 || { echo "$v failed"; tail -20 $OUT/b_${v}_$r.log; exit 1; }
+    WTP_LIB_PATH=$L timeout -k 10 300 python bench.py --full --config $CFG --no-cpu ${COLD:---no-cold} $X > $OUT/b_${v}_$r.log 2>&1 || { echo "$v failed"; tail -20 $OUT/b_${v}_$r.log; exit 1; }
     python3 - $OUT/b_${v}_$r.log $v $r <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); r = d['roofline']

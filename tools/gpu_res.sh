@@ -20,5 +20,5 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 "$OUT/gpu_$TAG.log"
 fi
 echo "== bench cfg2"
-timeout -k 10 300 python bench.py --no-cpu > "$OUT/bench_$TAG.log" 2>&1 || { echo bench failed; tail -30 "$OUT/bench_$TAG.log"; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu > "$OUT/bench_$TAG.log" 2>&1 || { echo bench failed; tail -30 "$OUT/bench_$TAG.log"; exit 1; }
 tail -1 "$OUT/bench_$TAG.log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('ms/step %.5f value %.4g frac %.3f avg_launch_us %.2f stamps %.2f cold %s' % (d['ms_per_step'], d['value'], r['frac'], r['avg_launch_us'], r['avg_launch_us_stamps'] or -1, (d.get('cold_mall') or {}).get('k_resident_us')))"
