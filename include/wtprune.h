@@ -16,6 +16,7 @@
  *   wtp_threshold_f32               percentile_based_thresholding     dwt_pruning.py:25-32
  *   wtp_wavedec2_f32                pywt.wavedec2 + coeffs_to_array   dwt_pruning.py:67-70
  *   wtp_waverec2_f32                array_to_coeffs + waverec2 + crop dwt_pruning.py:75-82
+ *   wtp_prune_abs_f32               multi_resolution_analysis         dwt_pruning_NoEntropy.py:29-60
  *   wtp_synth_f32                   (test/bench input generator, no reference counterpart)
  */
 #ifndef WTPRUNE_H
@@ -118,6 +119,48 @@ int wtp_prune_layers_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id
 size_t wtp_workspace_size_ex(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int flags);
 int wtp_prune_ex_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double pct, int flags,
                      void* workspace, size_t workspace_bytes, wtp_result* results_dev, wtp_stream_t stream);
+
+/* ---- the absolute-threshold method: multi_resolution_analysis of
+ * ResNet/dwt_pruning_NoEntropy.py:29-60 over a list of tensors ----
+ * Semantics per tensor, in order:
+ *   ndim < 2 : out = where(|w| < thr32, +0, w); the wavelet is not looked up
+ *   ndim >= 2: wavedec2(periodization, axes (-2,-1)) at the REQUESTED level (no clamp, no carry:
+ *              PyWavelets only warns above dwt_max_level, and lines shorter than the filter wrap
+ *              more than once); coeffs_to_array (zero padding where the packing is not tight);
+ *              every packed cell with |c| < thr32 becomes +0; waverec2; every axis cropped to
+ *              the original shape (a generic slice: odd 2-D tensors are valid, no WTP_ECROP).
+ * thr32 is the threshold rounded to the nearest float32 (NumPy 1.x compares a float32 array
+ * with a Python float in float32; overflow gives +inf): NaN, zero and negative thresholds
+ * prune nothing, +inf prunes every finite coefficient.
+ * Validation before any device work: unknown wavelet for an ndim >= 2 tensor WTP_EBADWAVELET,
+ * level < 0 WTP_EBADLEVEL, level > 32 WTP_EARG, an empty ndim >= 2 tensor WTP_EARG; an empty
+ * 1-D tensor is a no-op with a zeroed record.
+ * Tensors whose images are at most 8 x 8 all run in one launch that keeps each image on chip
+ * between its read and its write (path 1; groups of 64 tensors); larger ones run the filter-bank
+ * chain through a packed array in the workspace (path 2); ndim < 2 and level 0 of larger
+ * tensors are a plain mask (path 0).  Workspace: wtp_abs_workspace_size bytes (0 if the request
+ * is invalid); it needs no initialisation and a call of tiny tensors only needs the same few
+ * bytes whatever its batch.  It is plain scratch, written from its first byte and left as it
+ * is: it MUST NOT be the workspace of wtp_prune*_f32 / wtp_threshold_f32 / wtp_min_prune_f32,
+ * whose selection and barrier state at the start of that workspace has to stay as those
+ * entries leave it (a buffer that held an abs call needs wtp_workspace_init before they use it).  Stream-ordered, no allocation, no synchronisation, capturable;
+ * out may alias in. */
+typedef struct wtp_abs_result {   /* one per tensor, device memory */
+    int64_t numel;
+    int64_t nonzero_in;    /* torch.count_nonzero(weight): -0.0 is zero, NaN is non-zero */
+    int64_t nonzero_out;   /* torch.count_nonzero(pruned)                                */
+    int64_t coeff_numel;   /* packed coefficient array size (numel for ndim < 2)         */
+    uint32_t thr32_bits;   /* float32(threshold), the value the compare used             */
+    int32_t level;         /* the level that ran (the requested one; 0 for ndim < 2)     */
+    int32_t path;          /* 1 = fused tiny-image launch, 2 = filter-bank chain, 0 = plain mask */
+    int32_t reserved;
+} wtp_abs_result;
+#define WTP_ABS_PATH_MASK 0
+#define WTP_ABS_PATH_TINY 1
+#define WTP_ABS_PATH_CHAIN 2
+size_t wtp_abs_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level);
+int wtp_prune_abs_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double threshold,
+                      void* workspace, size_t workspace_bytes, wtp_abs_result* results_dev, wtp_stream_t stream);
 
 /* percentile_based_thresholding(arr, pct) on n device floats: out = where(|in| < thr, 0, in) */
 int wtp_threshold_f32(const float* in, float* out, int64_t n, double pct, void* workspace,

@@ -1,0 +1,399 @@
+"""GPU parity of the absolute-threshold method (wtp_prune_abs_f32; ResNet/dwt_pruning_NoEntropy.py)
+against the PyWavelets 1.1.1 + NumPy 1.26.4 goldens (tools/gen_golden_abs.py) and the C oracle on
+the same inputs, at UNCLAMPED levels: lines shorter than the filter, the one-launch tiny-image
+kernel, the filter-bank chain with its short levels in the per-point kernels, the plain mask.
+Bar: outputs bit for bit (np.array_equal and canon_hash), counts exact."""
+import csv
+import json
+import math
+import os
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+from tests import golden_io as G
+
+pytestmark = pytest.mark.gpu
+
+ABS = json.load(open(os.path.join(G.GOLDEN, "abs_manifest.json")))
+ARR = dict(np.load(os.path.join(G.GOLDEN, "abs_cases.npz")))
+MASK, TINY, CHAIN = 0, 1, 2
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from wavelettransforms_amd import engine
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return engine
+
+
+def _oracle(x, wavelet, level, thr):
+    """The unchanged oracle as the yardstick (tests/test_abs_threshold_host.py pins it to the goldens)."""
+    thr32 = np.float32(thr)
+    if x.ndim < 2:
+        return np.where(np.abs(x) < thr32, np.float32(0), x)
+    return O.waverec2_packed(O.wavedec2_packed(x, wavelet, level), x.shape, wavelet, level, thr32)
+
+
+def _zeroed_fraction(x, wavelet, level, thr):
+    """Share of the packed cells below the threshold (padding cells included): the case is not trivial."""
+    return float((np.abs(O.wavedec2_packed(x, wavelet, level)) < np.float32(thr)).mean())
+
+
+def _expected_path(shape, level):
+    if len(shape) < 2:
+        return MASK
+    if shape[-2] <= 8 and shape[-1] <= 8:
+        return TINY
+    return CHAIN if level > 0 else MASK
+
+
+def _check(x, ref, out, r, wavelet, level, thr, tag):
+    shape = x.shape
+    assert out.shape == shape and out.dtype == np.float32, tag
+    assert np.array_equal(out, ref), tag
+    assert G.canon_hash(out) == G.canon_hash(ref), tag
+    assert r["numel"] == x.size, tag
+    assert r["nonzero_in"] == int(np.count_nonzero(x)), tag
+    assert r["nonzero_out"] == int(np.count_nonzero(ref)), tag
+    assert r["thr32_bits"] == G.f32_bits(thr), tag
+    assert r["path"] == _expected_path(shape, level), (tag, r["path"])
+    if len(shape) >= 2:
+        pr, pc = O.packed_shape(shape[-2], shape[-1], level)
+        assert r["coeff_numel"] == x.size // (shape[-2] * shape[-1]) * pr * pc, tag
+        assert r["level"] == level, tag
+    else:
+        assert r["coeff_numel"] == x.size and r["level"] == 0, tag
+
+
+def _run_and_check(eng, xs_np, wavelet, level, thr, tag, refs=None):
+    xs = [torch.from_numpy(x).cuda() for x in xs_np]
+    outs, res = eng.prune_abs(xs, wavelet, level, thr)
+    for i, (x, o, r) in enumerate(zip(xs_np, outs, res)):
+        ref = refs[i] if refs is not None else _oracle(x, wavelet, level, thr)
+        _check(x, ref, o.cpu().numpy(), r, wavelet, level, thr, (tag, x.shape))
+        assert np.array_equal(xs[i].cpu().numpy(), x), "out of place: the input is untouched"
+    return outs, res
+
+
+def test_golden_cases(eng):
+    """Every golden, grouped by (wavelet, level, threshold) into one batched call each: tiny images,
+    chain tensors and a 1-D tensor side by side."""
+    groups = {}
+    for name, rec in ABS["cases"].items():
+        groups.setdefault((rec["wavelet"], rec["level"], rec["threshold"]), []).append(name)
+    assert len(groups) >= 18
+    for (wavelet, level, thr), names in sorted(groups.items()):
+        recs = [ABS["cases"][n] for n in names]
+        xs = [ARR[n + "/in"] if n + "/in" in ARR else G.W.synth_numpy(tuple(r["shape"]), *r["synth"])
+              for n, r in zip(names, recs)]
+        outs, res = _run_and_check(eng, xs, wavelet, level, thr, (wavelet, level, thr),
+                                   refs=[ARR[n + "/out"] for n in names])
+        for n, rec, o, r in zip(names, recs, outs, res):
+            assert G.canon_hash(o.cpu().numpy()) == rec["out_hash"], n
+            assert (r["nonzero_in"], r["nonzero_out"]) == (rec["nonzero_in"], rec["nonzero_out"]), n
+            assert r["thr32_bits"] == rec["thr32_bits"], n
+            assert r["coeff_numel"] == int(np.prod(rec["packed_shape"])), n
+
+
+TINY_SHAPES = [(8, 3, 1, 1), (67, 3, 3, 3), (1, 1, 3, 3), (4, 3, 7, 7), (5, 2, 5, 5), (3, 2, 2, 3), (6, 1, 8, 8)]
+TINY_SETTINGS = [("haar", 5), ("db2", 2), ("bior3.3", 5), ("db8", 1), ("db8", 5), ("bior3.3", 0)]
+
+
+@pytest.mark.parametrize("wavelet,level", TINY_SETTINGS)
+def test_tiny_images_one_call(eng, wavelet, level):
+    """All tiny shapes of a setting and a 1-D (64,) tensor in ONE call: the tensor boundaries fall
+    between the launch's waves, the batches (24, 201, 1, 12, 10, 6, 6 images) are no multiples of
+    64.  A call has one threshold, so every input of this call is drawn at the sigma of the
+    (67, 3, 3, 3) kernel and the threshold is 0.6745 of it (the median of |N(0, sigma)|: about
+    half of the cells go); test_tiny_images_own_sigma runs each shape at its own sigma."""
+    sigma = G.W.conv_sigma((67, 3, 3, 3))
+    e = G.W.sigma_exponent(sigma)
+    xs = [G.W.synth_numpy(s, 71, i, e) for i, s in enumerate(TINY_SHAPES + [(64,)])]
+    _, res = _run_and_check(eng, xs, wavelet, level, 0.6745 * sigma, (wavelet, level))
+    assert [r["path"] for r in res] == [TINY] * len(TINY_SHAPES) + [MASK]
+    # a guard of the test's own inputs, not of the product: at this common sigma the oracle zeroes
+    # 0.11 (8 x 8 at level 0) to 0.97 (1 x 1 at level 5, mostly padding cells) of the packed cells
+    for x in xs[:-1]:
+        assert 0.1 < _zeroed_fraction(x, wavelet, level, 0.6745 * sigma) < 0.98, x.shape
+
+
+@pytest.mark.parametrize("wavelet,level", TINY_SETTINGS)
+def test_tiny_images_own_sigma(eng, wavelet, level):
+    """Each tiny shape at threshold 0.6745 x conv_sigma(shape), inputs at that sigma."""
+    for i, s in enumerate(TINY_SHAPES):
+        sigma = G.W.conv_sigma(s)
+        x = G.W.synth_numpy(s, 72, i, G.W.sigma_exponent(sigma))
+        _run_and_check(eng, [x], wavelet, level, 0.6745 * sigma, (wavelet, level))
+        # a guard of the inputs: with these seeds the oracle zeroes 0.391 to 0.975 of the packed
+        # cells (the synthetic sigma is a power of two near conv_sigma, so the share at level 0
+        # is not exactly one half)
+        assert 0.39 < _zeroed_fraction(x, wavelet, level, 0.6745 * sigma) < 0.98, s
+
+
+@pytest.mark.parametrize("shape,wavelet,level,path", [
+    ((64, 8), "db8", 3, CHAIN),           # 8 columns under a 16-tap filter: per-point at every level
+    ((33, 17), "db4", 2, CHAIN),          # odd 2-D: a generic crop, no error
+    ((256, 256), "db8", 8, CHAIN),        # tiled down to 32 x 32, per-point below, three 1 -> 1 levels
+    ((2, 96, 100), "bior3.3", 3, CHAIN),
+    ((128, 784), "rbio2.2", 3, CHAIN),
+    ((3, 2, 8, 8), "db2", 3, TINY),       # the tiny limit and its neighbours
+    ((3, 2, 8, 9), "db2", 3, CHAIN),
+    ((3, 2, 9, 9), "db2", 3, CHAIN),
+])
+def test_filter_bank_chain(eng, shape, wavelet, level, path):
+    sigma = 1.0 / math.sqrt(shape[-1])
+    x = G.W.synth_numpy(shape, 73, 0, G.W.sigma_exponent(sigma))
+    _, res = _run_and_check(eng, [x], wavelet, level, 0.6745 * sigma, (shape, wavelet, level))
+    assert res[0]["path"] == path
+    # a guard of the inputs: the oracle zeroes 0.44 ((256, 256)) to 0.67 ((3, 2, 9, 9)) of the cells
+    assert 0.43 < _zeroed_fraction(x, wavelet, level, 0.6745 * sigma) < 0.68
+
+
+def _mixed_inputs():
+    shapes = [(67, 3, 3, 3), (33, 17), (64,), (4, 3, 7, 7), (3, 2, 8, 9), (130, 5, 1, 1)]
+    e = G.W.sigma_exponent(0.05)
+    return [G.W.synth_numpy(s, 74, i, e) for i, s in enumerate(shapes)]
+
+
+def test_more_tiny_tensors_than_one_launch_table(eng):
+    """The tensors of a k_abs_tiny launch are its kernel argument, 64 at most: a list of 150 tiny
+    tensors (with 1-D and chain tensors between them) takes three launches, whose wave numbering
+    restarts while the record indices run on."""
+    e = G.W.sigma_exponent(0.05)
+    shapes = []
+    for i in range(150):
+        shapes.append([(3 + i % 5, 2, 3, 3), (2, 1 + i % 3, 7, 7), (70 + i, 1, 1, 1), (1, 1, 2, 5)][i % 4])
+        if i in (10, 63, 64, 127, 128):
+            shapes.append((17,) if i % 2 else (9, 11))
+    xs = [G.W.synth_numpy(s, 76, i, e) for i, s in enumerate(shapes)]
+    _, res = _run_and_check(eng, xs, "bior3.3", 5, 0.0337, "150 tiny")
+    assert sum(r["path"] == TINY for r in res) == 150
+
+
+def test_percentile_calls_around_an_abs_call(eng):
+    """The percentile entries keep selection and barrier state at the start of their workspace;
+    the absolute-threshold entry uses its workspace as plain scratch.  The engine gives it a
+    workspace of its own, so percentile calls before and after an abs call with chain and 1-D
+    tensors on one stream are bit for bit the oracle's."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ts = G.W.resnet18_tensors(0)[1:7]
+    conv_np = [G.W.synth_numpy(s, seed, tid, e) for _, s, seed, tid, e in ts]
+    big_np = [G.W.synth_numpy((600, 700), 77, 0, G.W.sigma_exponent(0.04))]
+    abs_np = [G.W.synth_numpy(s, 77, 1 + i, G.W.sigma_exponent(0.05))
+              for i, s in enumerate([(128, 784), (33, 17), (301,), (64, 3, 3, 3)])]
+
+    def percentile_round():
+        got = []
+        for xs_np, wavelet, level, pct in ((conv_np, "bior3.3", 5, 50.0), (big_np, "db4", 3, 61.8)):
+            outs, res = eng.prune([torch.from_numpy(x).cuda() for x in xs_np], wavelet, level, pct, carry_level=False)
+            for x, o, r in zip(xs_np, outs, res):
+                ref, rr = O.prune_tensor(x, wavelet, level, pct)
+                assert np.array_equal(o.cpu().numpy(), ref), (x.shape, wavelet)
+                assert r["zero_count"] == rr["zero_count"] and G.f64_bits_equal(r["thr64"], rr["thr64"])
+                got.append((o.cpu().numpy(), r))
+        return got
+
+    first = percentile_round()
+    ws = eng.workspace(dev, 256)
+    _run_and_check(eng, abs_np, "db4", 2, 0.0337, "between percentile calls")
+    assert eng.workspace(dev, 256) is ws, "the percentile workspace is the one from before the abs call"
+    assert eng.workspace(dev, 256, kind="abs").data_ptr() != ws.data_ptr()
+    second = percentile_round()
+    for (o1, r1), (o2, r2) in zip(first, second):
+        assert np.array_equal(o1, o2) and r1 == r2
+
+
+def test_in_place_equals_out_of_place(eng):
+    xs_np = _mixed_inputs()
+    outs, res = _run_and_check(eng, xs_np, "bior3.3", 5, 0.0337, "mixed")
+    ys = [torch.from_numpy(x).cuda() for x in xs_np]
+    outs2, res2 = eng.prune_abs(ys, "bior3.3", 5, 0.0337, outs=ys)
+    assert all(a is b for a, b in zip(outs2, ys))
+    for o, y in zip(outs, ys):
+        assert np.array_equal(o.cpu().numpy(), y.cpu().numpy())
+    assert res2 == res  # nonzero_in is counted before the output is written
+
+
+def test_graph_capture_replays_on_refreshed_inputs(eng):
+    a_np, b_np = _mixed_inputs(), [x[::-1].copy() if x.ndim == 1 else -x for x in _mixed_inputs()]
+    ref_a = eng.prune_abs([torch.from_numpy(x).cuda() for x in a_np], "db2", 3, 0.0337)
+    ref_b = eng.prune_abs([torch.from_numpy(x).cuda() for x in b_np], "db2", 3, 0.0337)
+    xs = [torch.from_numpy(x).cuda() for x in a_np]
+    outs = [torch.empty_like(x) for x in xs]
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):  # warm-up: the workspace exists before the capture
+        eng.launch_abs(xs, "db2", 3, 0.0337, outs=outs, stream=s)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        with torch.cuda.graph(g, stream=s):
+            _, resd = eng.launch_abs(xs, "db2", 3, 0.0337, outs=outs)
+    for inputs, (ref_outs, ref_res) in ((b_np, ref_b), (a_np, ref_a)):
+        for x, v in zip(xs, inputs):
+            x.copy_(torch.from_numpy(v))
+        for o in outs:
+            o.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        assert eng.decode_abs(resd, len(xs)) == ref_res
+        for o, r in zip(outs, ref_outs):
+            assert np.array_equal(o.cpu().numpy(), r.cpu().numpy())
+
+
+def test_threshold_values(eng):
+    """0, negative and NaN thresholds prune nothing; +inf (and 1e40, which rounds to +inf in
+    float32) prunes every finite coefficient; float32(0.7) is not below 0.7; -0.0 is a zero."""
+    e = G.W.sigma_exponent(0.05)
+    xs_np = [G.W.synth_numpy((5, 3, 3, 3), 75, 0, e), G.W.synth_numpy((33, 17), 75, 1, e), G.W.synth_numpy((40,), 75, 2, e)]
+    xs = [torch.from_numpy(x).cuda() for x in xs_np]
+    for thr in (0.0, -1.0, float("nan")):
+        outs, res = eng.prune_abs(xs, "db2", 2, thr)
+        for x, o, r in zip(xs_np, outs, res):
+            ref = _oracle(x, "db2", 2, 0.0)  # nothing masked: the transform pair's own rounding only
+            assert np.array_equal(o.cpu().numpy(), ref)
+            assert r["nonzero_in"] == int(np.count_nonzero(x)) and r["nonzero_out"] == int(np.count_nonzero(ref))
+            assert G.f32_bits(r["thr32"]) == G.f32_bits(thr) or (math.isnan(thr) and math.isnan(r["thr32"]))
+    for thr in (float("inf"), 1e40):
+        outs, res = eng.prune_abs(xs, "db2", 2, thr)
+        for o, r in zip(outs, res):
+            assert not o.cpu().numpy().any() and r["nonzero_out"] == 0
+            assert r["thr32"] == float("inf")
+    for name in ("abs_special_1d", "abs_special_level0"):
+        rec, x = ABS["cases"][name], ARR[name + "/in"]
+        outs, res = eng.prune_abs([torch.from_numpy(x).cuda()], rec["wavelet"], rec["level"], 0.7)
+        out = outs[0].cpu().numpy()
+        assert np.array_equal(out, ARR[name + "/out"])
+        keep = x == np.float32(0.7)
+        assert keep.any() and np.array_equal(out[keep], x[keep])
+        assert res[0]["nonzero_in"] == rec["nonzero_in"] == x.size - 2  # -0.0 and 0.0; the denormals count
+        assert res[0]["nonzero_out"] == rec["nonzero_out"]
+
+
+def test_validation_through_the_engine(eng):
+    x = torch.zeros(4, 4, 3, 3, device="cuda")
+    with pytest.raises(ValueError, match="Unknown wavelet name 'nosuch'"):
+        eng.prune_abs([x], "nosuch", 1, 0.1)
+    with pytest.raises(ValueError, match="Level value of -1 is too low"):
+        eng.prune_abs([x], "haar", -1, 0.1)
+    outs, res = eng.prune_abs([torch.zeros(0, device="cuda"), x], "haar", 1, 0.1)
+    assert res[0] == dict(numel=0, nonzero_in=0, nonzero_out=0, coeff_numel=0, thr32_bits=0, level=0, path=0,
+                          thr32=0.0, pruned=0)
+    assert res[1]["numel"] == 144 and res[1]["nonzero_in"] == 0
+
+
+@pytest.fixture(scope="module")
+def resnet_refs():
+    """The ResNet-18 conv list through the oracle, once (about 6 s of CPU time)."""
+    ts = G.W.resnet18_tensors(0)
+    xs = [G.W.synth_numpy(s, seed, tid, e) for _, s, seed, tid, e in ts]
+    return ts, xs, [_oracle(x, "bior3.3", 5, 0.0125) for x in xs]
+
+
+def test_resnet18_one_call(eng, resnet_refs):
+    """The headline workload under this method: five real levels on every 7 x 7, 3 x 3 and 1 x 1
+    kernel (the percentile path clamps it to level 0), the whole list in one call and one launch."""
+    ts, xs_np, refs = resnet_refs
+    xs = [eng.synth(s, seed, tid, e) for _, s, seed, tid, e in ts]
+    outs, res = eng.prune_abs(xs, "bior3.3", 5, 0.0125)
+    for (name, *_), x, ref, o, r in zip(ts, xs_np, refs, outs, res):
+        _check(x, ref, o.cpu().numpy(), r, "bior3.3", 5, 0.0125, name)
+        assert r["path"] == TINY and r["level"] == 5, name
+
+
+def test_mirror_multi_resolution_analysis(eng, resnet_refs):
+    from wavelettransforms_amd import dwt_pruning_NoEntropy as D
+    ts, xs_np, refs = resnet_refs
+    pick = [0, 1, 5]
+    ws = [torch.from_numpy(xs_np[i]) for i in pick] + [torch.from_numpy(xs_np[1][0, 0, 0]).cuda()]
+    with pytest.warns(UserWarning, match="Level value of 5 is too high: all coefficients will experience boundary effects."):
+        outs, total = D.multi_resolution_analysis(ws, "bior3.3", 5, 0.0125)
+    want = 0
+    for w, o, i in zip(ws[:3], outs[:3], pick):
+        assert o.device == w.device and o.dtype == w.dtype and o.shape == w.shape
+        assert np.array_equal(o.numpy(), refs[i])
+        want += int(np.count_nonzero(xs_np[i])) - int(np.count_nonzero(refs[i]))
+    b = xs_np[1][0, 0, 0]
+    assert outs[3].is_cuda and np.array_equal(outs[3].cpu().numpy(), _oracle(b, "bior3.3", 5, 0.0125))
+    want += int(np.count_nonzero(b)) - int(np.count_nonzero(_oracle(b, "bior3.3", 5, 0.0125)))
+    assert total == want and isinstance(total, int)
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")  # level 1 of a 7 x 7 kernel under haar is within dwt_max_level
+        D.multi_resolution_analysis(ws[:1], "haar", 1, 0.0125)
+
+
+def test_mirror_prune_layer_weights(eng):
+    from wavelettransforms_amd import dwt_pruning_NoEntropy as D
+    torch.manual_seed(5)
+    layer = torch.nn.Conv2d(3, 8, 3, bias=True).cuda()
+    with torch.no_grad():
+        layer.bias.copy_(torch.tensor([0.5, -0.01, 0.02, -0.3, 0.0, 0.011, -0.0125, 0.0124]))
+    w0, b0 = layer.weight.detach().cpu().numpy().copy(), layer.bias.detach().cpu().numpy().copy()
+    wref, bref = _oracle(w0, "db2", 2, 0.0125), _oracle(b0, "db2", 2, 0.0125)
+    with pytest.warns(UserWarning, match="too high"):
+        numel, nonzero_before, pruned = D.prune_layer_weights(layer, "db2", 2, 0.0125)
+    assert numel == w0.size + b0.size
+    assert nonzero_before == int(np.count_nonzero(w0)) + int(np.count_nonzero(b0))   # BEFORE pruning (:81)
+    assert pruned == nonzero_before - int(np.count_nonzero(wref)) - int(np.count_nonzero(bref))
+    assert np.array_equal(layer.weight.detach().cpu().numpy(), wref)
+    assert np.array_equal(layer.bias.detach().cpu().numpy(), bref)                   # the bias is thresholded
+    assert bref.tolist() == [0.5, 0.0, np.float32(0.02), np.float32(-0.3), 0.0, 0.0, np.float32(-0.0125), 0.0]
+    # a frozen parameter is counted and pruned in the returned numbers, but left as it is (:88-89)
+    layer2 = torch.nn.Conv2d(3, 8, 3, bias=True).cuda()
+    layer2.weight.requires_grad_(False)
+    w2 = layer2.weight.detach().clone()
+    b2 = layer2.bias.detach().cpu().numpy().copy()
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        _, _, pruned2 = D.prune_layer_weights(layer2, "db2", 2, 0.05)
+    assert torch.equal(layer2.weight, w2)
+    assert np.array_equal(layer2.bias.detach().cpu().numpy(), _oracle(b2, "db2", 2, 0.05))
+    assert pruned2 > 0
+
+
+def test_mirror_wavelet_pruning(eng, tmp_path, capsys):
+    from wavelettransforms_amd import dwt_pruning_NoEntropy as D
+    torch.manual_seed(6)
+    model = torch.nn.Sequential(torch.nn.Conv2d(3, 8, 3, bias=True), torch.nn.ReLU(), torch.nn.Linear(4, 4),
+                                torch.nn.Conv2d(8, 4, 1, bias=False)).cuda()
+    convs = [(n, m) for n, m in model.named_modules() if isinstance(m, torch.nn.Conv2d)]
+    before = {n: [p.detach().cpu().numpy().copy() for p in m.parameters()] for n, m in convs}
+    lin = model[2].weight.detach().clone()
+    work = tmp_path / "a" / "b"  # outputs go to <cwd>/../../WaveletTransforms/ResNet/SavedModels
+    work.mkdir(parents=True)
+    cwd = os.getcwd()
+    os.chdir(work)
+    try:
+        exp_csv = str(tmp_path / "experiment_log.csv")
+        with pytest.warns(UserWarning, match="Level value of 5 is too high"):
+            log_path = D.wavelet_pruning(model, "bior3.3", 5, 0.0125, exp_csv, "abs0guid")
+    finally:
+        os.chdir(cwd)
+    root = tmp_path / "WaveletTransforms" / "ResNet" / "SavedModels" / "bior3.3_threshold-0.0125_level-5_guid-abs0"
+    assert os.path.samefile(log_path, root / "selective_pruned" / "log.csv")   # the raw threshold, no / 100
+    rows = list(csv.DictReader(open(log_path)))
+    assert [r["Layer Name"] for r in rows] == [n for n, _ in convs]
+    tot_pruned = tot_nonzero = 0
+    for (name, m), r in zip(convs, rows):
+        refs = [_oracle(p, "bior3.3", 5, 0.0125) for p in before[name]]
+        for p, ref in zip(m.parameters(), refs):
+            assert np.array_equal(p.detach().cpu().numpy(), ref), name
+        nz = sum(int(np.count_nonzero(p)) for p in before[name])
+        pruned = nz - sum(int(np.count_nonzero(ref)) for ref in refs)
+        assert (r["GUID"], r["Wavelet"], r["Level"], r["Threshold"], r["DWT Phase"]) == ("abs0guid", "bior3.3", "5", "0.0125", "selective")
+        assert int(r["Original Parameter Count"]) == sum(p.size for p in before[name])
+        assert int(r["Non-zero Params"]) == nz and int(r["Total Pruned Count"]) == pruned
+        tot_pruned += pruned
+        tot_nonzero += nz
+    assert torch.equal(model[2].weight, lin)  # Conv2d modules only
+    exp = list(csv.reader(open(exp_csv)))
+    assert exp[1][:7] == ["abs0guid", "bior3.3", "5", "0.0125", "selective", str(tot_pruned), str(tot_nonzero)]
+    assert os.path.samefile(exp[1][7], root / "selective_pruned")
+    assert (root / "selective_pruned" / "model.safetensors").exists()
+    assert "Selectively pruned model saved at" in capsys.readouterr().out

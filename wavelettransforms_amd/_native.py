@@ -36,7 +36,14 @@ class WtpResult(ctypes.Structure):
                 ("eff_level", ctypes.c_int32), ("path", ctypes.c_int32)]
 
 
+class WtpAbsResult(ctypes.Structure):
+    _fields_ = [("numel", ctypes.c_int64), ("nonzero_in", ctypes.c_int64), ("nonzero_out", ctypes.c_int64),
+                ("coeff_numel", ctypes.c_int64), ("thr32_bits", ctypes.c_uint32), ("level", ctypes.c_int32),
+                ("path", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 RESULT_BYTES = ctypes.sizeof(WtpResult)
+ABS_RESULT_BYTES = ctypes.sizeof(WtpAbsResult)
 _lib = None
 
 
@@ -69,6 +76,8 @@ def lib():
             "wtp_prune_layers_f32": ([tp, i32, i32, i32, f64, vp, sz, vp, vp], i32),
             "wtp_workspace_size_ex": ([tp, i32, i32, i32, i32], sz),
             "wtp_prune_ex_f32": ([tp, i32, i32, i32, f64, i32, vp, sz, vp, vp], i32),
+            "wtp_abs_workspace_size": ([tp, i32, i32, i32], sz),
+            "wtp_prune_abs_f32": ([tp, i32, i32, i32, f64, vp, sz, vp, vp], i32),
             "wtp_threshold_f32": ([vp, vp, i64, f64, vp, sz, vp, vp], i32),
             "wtp_dwt_workspace_size": ([i64, i64, i64, i32], sz),
             "wtp_wavedec2_f32": ([vp, vp, i64, i64, i64, i32, i32, vp, sz, vp], i32),

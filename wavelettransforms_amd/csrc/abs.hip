@@ -1,0 +1,187 @@
+/*
+ * abs.hip -- device side of the absolute-threshold method (ResNet/dwt_pruning_NoEntropy.py:29-60,
+ * wtp_prune_abs_f32): the threshold is a given number, so nothing is selected and a tensor is one
+ * streaming pass.
+ *
+ *   k_abs_tiny   every tensor of the call whose images are at most 8 x 8 (conv kernels), in one
+ *                launch: an image is read once, all levels forward, the mask, all levels inverse
+ *                and the crop run in LDS, and it is written once (8 B of HBM per weight).
+ *   k_abs_count  count_nonzero of a tensor (the filter-bank chain's and the plain mask's records).
+ *
+ * k_abs_tiny gives a whole wave to one tensor, one image per lane, in a sample-major LDS layout
+ * (word s of an image at lds[s * NL + lane]): (H, W, level, F) are wave-uniform, so the wrapped
+ * sample index of every (output, tap) is scalar arithmetic and every LDS access is a uniform
+ * offset plus the lane.  Lines here are shorter than the filter (a 3 x 3 kernel under an 8-tap
+ * bior3.3 at level 5 ends in four 1 -> 1 levels): every tap is still multiplied and added on its
+ * own, in wt_dwt_core.h's order (wt_abs_core.h: abs_image, shared with the host-side check).
+ */
+#include "wtp_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace wtp {
+
+/* torch.count_nonzero's test on the bit pattern (a denormal is non-zero whatever the FP mode) */
+__device__ __forceinline__ unsigned abs_nonzero(float v) { return (__float_as_uint(v) << 1) != 0u; }
+
+__device__ __forceinline__ unsigned abs_wave_sum(unsigned v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(ABS_THREADS) void k_abs_tiny(AbsTable t, wtp_abs_result* __restrict__ res) {
+    __shared__ float lds[ABS_WAVE_WORDS];
+    /* the four filters beside the arena: a tap is a broadcast LDS read that returns in order with
+     * the sample reads, so an unrolled tap loop keeps several reads in flight (a scalar load per
+     * tap from the kernel argument returns out of order: every tap then waits for all of them) */
+    __shared__ float ltap[ABS_TAP_WORDS];
+    const int gw = blockIdx.x;
+    int sg = 0;
+    for (int i = 1; i < t.nseg; ++i) sg += gw >= t.wave_begin[i];
+    const AbsSeg& S = t.s[sg];
+    const int H = S.H, W = S.W, L = S.L, NL = 1 << S.nl_log2, F = t.tp.F, HW = H * W;
+    const int w = gw - t.wave_begin[sg];
+    const int64_t b0 = (int64_t)w * NL;
+    const int nimg = (int)(S.B - b0 < NL ? S.B - b0 : NL);
+    const float thr = __uint_as_float(t.thr_bits);
+    const float* in = S.in + b0 * HW; /* may alias out: the wave reads all of its range before it writes */
+    float* out = S.out + b0 * HW;
+    const int lane = threadIdx.x;
+    const int total = nimg * HW;
+
+    /* areas (wt_abs_core.h): A the image / a level's approximation, T a level's two half
+     * transforms, D the masked coefficients */
+    float* A = lds;
+    float* T = A + abs_area_a(H, W, L) * NL;
+    float* D = T + abs_area_t(H, W, L) * NL;
+
+    const int FP = ABS_TAP_WORDS / 4;
+    for (int e = threadIdx.x; e < 4 * F; e += ABS_THREADS) {
+        const int k = e / F, j = e - k * F;
+        ltap[k * FP + j] = t.tp.f[k][j];
+    }
+    /* coalesced read of the wave's images into the sample-major layout */
+    unsigned z_in = 0, z_out = 0;
+    for (int e = lane; e < total; e += ABS_THREADS) {
+        const float v = in[e];
+        const int img = e / HW, s = e - img * HW;
+        A[s * NL + img] = v;
+        z_in += !abs_nonzero(v);
+    }
+    __syncthreads();
+
+    if (lane < nimg)
+        abs_image(A + lane, T + lane, D + lane, NL, H, W, L, F, ltap, ltap + FP, ltap + 2 * FP, ltap + 3 * FP, thr);
+    __syncthreads();
+
+    for (int e = lane; e < total; e += ABS_THREADS) {
+        const int img = e / HW, s = e - img * HW;
+        const float v = A[s * NL + img];
+        out[e] = v;
+        z_out += !abs_nonzero(v);
+    }
+    /* the counts as numel minus the zeros: the tensor's first wave adds numel, every wave takes
+     * off the zeros it saw -- usually none, so a tensor costs two atomics, not two per wave (the
+     * ResNet-18 list: 39 000 adds on 40 addresses, 28 us of a 583 us launch) */
+    z_in = abs_wave_sum(z_in);
+    z_out = abs_wave_sum(z_out);
+    if (lane == 0) {
+        wtp_abs_result* r = res + S.res;
+        if (z_in) atomicAdd((unsigned long long*)&r->nonzero_in, 0ull - (unsigned long long)z_in);
+        if (z_out) atomicAdd((unsigned long long*)&r->nonzero_out, 0ull - (unsigned long long)z_out);
+        if (w == 0) { /* ... and the record's fixed fields (the record starts from the call's zero fill) */
+            atomicAdd((unsigned long long*)&r->nonzero_in, (unsigned long long)S.B * HW);
+            atomicAdd((unsigned long long*)&r->nonzero_out, (unsigned long long)S.B * HW);
+            int PR = H, PC = W; /* wt_geom's packed size */
+            if (L) {
+                int R = H, C = W;
+                PR = PC = 0;
+                for (int k = 1; k <= L; ++k) {
+                    R = (R + 1) >> 1;
+                    C = (C + 1) >> 1;
+                    PR += R;
+                    PC += C;
+                }
+                PR += R;
+                PC += C;
+            }
+            r->numel = (int64_t)S.B * HW;
+            r->coeff_numel = (int64_t)S.B * PR * PC;
+            r->thr32_bits = t.thr_bits;
+            r->level = L;
+            r->path = WTP_ABS_PATH_TINY;
+            r->reserved = 0;
+        }
+    }
+}
+
+/* count_nonzero(x) added to *dst (-0.0 is zero, NaN is non-zero): one atomic per wave.  The
+ * first pass of a tensor also writes its record's fixed fields. */
+__global__ __launch_bounds__(ABS_COUNT_THREADS) void k_abs_count(const float* __restrict__ x, int64_t n,
+                                                                 unsigned long long* __restrict__ dst,
+                                                                 wtp_abs_result* __restrict__ rec, wtp_abs_result init) {
+    unsigned c = 0;
+    for (int64_t i = (int64_t)blockIdx.x * ABS_COUNT_THREADS + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * ABS_COUNT_THREADS)
+        c += abs_nonzero(x[i]);
+    c = abs_wave_sum(c);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(dst, (unsigned long long)c);
+    if (rec && blockIdx.x == 0 && threadIdx.x == 0) {
+        rec->numel = init.numel;
+        rec->coeff_numel = init.coeff_numel;
+        rec->thr32_bits = init.thr32_bits;
+        rec->level = init.level;
+        rec->path = init.path;
+        rec->reserved = 0;
+    }
+}
+
+/* The call's first launch: every record zero (the counts are accumulated; an empty tensor's
+ * record stays zero) and the float32 threshold in its workspace word for the kernels that read
+ * it from memory.  A kernel, not hipMemsetAsync: with a memset node in its place the records were
+ * not zero when a captured graph of the call replayed (eager calls were right); the cause was
+ * not established. */
+__global__ __launch_bounds__(ABS_COUNT_THREADS) void k_abs_init(uint32_t* __restrict__ rec_words, int64_t nwords,
+                                                                uint32_t* __restrict__ thr_word, uint32_t thr_bits) {
+    for (int64_t i = (int64_t)blockIdx.x * ABS_COUNT_THREADS + threadIdx.x; i < nwords;
+         i += (int64_t)gridDim.x * ABS_COUNT_THREADS)
+        rec_words[i] = 0u;
+    if (thr_word && blockIdx.x == 0 && threadIdx.x == 0) *thr_word = thr_bits;
+}
+
+/* zero padding of a packed array that is not tight (pywt.coeffs_to_array) */
+__global__ __launch_bounds__(ABS_COUNT_THREADS) void k_abs_zero(float* __restrict__ p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * ABS_COUNT_THREADS + threadIdx.x; i < n;
+         i += (int64_t)gridDim.x * ABS_COUNT_THREADS)
+        p[i] = 0.0f;
+}
+
+static unsigned abs_grid(int64_t n, int per_thread) {
+    int64_t blocks = (n + (int64_t)ABS_COUNT_THREADS * per_thread - 1) / ((int64_t)ABS_COUNT_THREADS * per_thread);
+    if (blocks < 1) blocks = 1;
+    if (blocks > 4096) blocks = 4096;
+    return (unsigned)blocks;
+}
+
+void launch_abs_init(wtp_abs_result* res, int n, float* thr_word, uint32_t thr_bits, hipStream_t s) {
+    const int64_t nwords = (int64_t)n * (int64_t)(sizeof(wtp_abs_result) / 4);
+    hipLaunchKernelGGL(k_abs_init, dim3(abs_grid(nwords, 4)), dim3(ABS_COUNT_THREADS), 0, s,
+                       reinterpret_cast<uint32_t*>(res), nwords, reinterpret_cast<uint32_t*>(thr_word), thr_bits);
+}
+
+void launch_abs_zero(float* p, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(k_abs_zero, dim3(abs_grid(n, 16)), dim3(ABS_COUNT_THREADS), 0, s, p, n);
+}
+
+void launch_abs_tiny(const AbsTable& t, wtp_abs_result* res, hipStream_t s) {
+    hipLaunchKernelGGL(k_abs_tiny, dim3((unsigned)t.nwave), dim3(ABS_THREADS), 0, s, t, res);
+}
+
+void launch_abs_count(const float* x, int64_t n, unsigned long long* dst, wtp_abs_result* rec,
+                      const wtp_abs_result& init, hipStream_t s) {
+    /* a thread takes at most 2^31 elements: the per-thread count stays in 32 bits */
+    hipLaunchKernelGGL(k_abs_count, dim3(abs_grid(n, 16)), dim3(ABS_COUNT_THREADS), 0, s, x, n, dst, rec, init);
+}
+
+}  // namespace wtp

@@ -91,6 +91,7 @@ struct TPlan {
     int64_t f_slots = 0;  /* fused selection: k_fwd_int wave slots of its forward (0: never fused) */
     size_t f_off = 0;     /* workspace byte offset of its slot area (per group parity and slot) */
     int64_t len[34] = {}; /* flat: len[0] = numel, len[k] = ceil(len[k-1] / 2)              */
+    bool strict = false;  /* unclamped levels (wtp_prune_abs_f32): lvl_tiled keeps short sides per-point */
 };
 
 struct Layout {
@@ -211,6 +212,17 @@ int plan_tensors(const wtp_tensor* ts, int n, int wid, int level, double pct, bo
     return WTP_OK;
 }
 
+/* Whether one level of p, whose larger side (the analysis input / the synthesis output) is
+ * (B, R, C), runs in the tiled kernels.  The percentile path clamps the level, so its levels
+ * always have an input of at least 2 (F - 1) and an output of at least F - 1 samples a side, and
+ * the tiled kernels were written for that (k_inv_int's edge form wraps a coordinate once).  A
+ * plan with unclamped levels (strict) holds every level to the same bound: shorter sides take
+ * the per-point kernels, which wrap any number of times (wt_dwt_core.h). */
+bool lvl_tiled(const TPlan& p, int64_t B, int64_t R, int64_t C, const Taps& tp) {
+    if (!fb_tiled_ok(B, R, C, tp)) return false;
+    return !p.strict || std::min(R, C) >= 2 * (int64_t)(tp.F - 1);
+}
+
 /* Elements one level temp of tensor p needs: the largest intermediate its forward and inverse
  * write to a temp, level by level, with the kernels forward_chains / inverse_chains pick (tiled:
  * the next approximation / the synthesis output below level 1; per-point: the column pass's two
@@ -220,8 +232,8 @@ size_t temp_elems(const TPlan& p, const Taps& tp) {
     int64_t need = 0;
     for (int k = 1; k <= p.L; ++k) {
         const int64_t R0 = p.g.R[k - 1], C0 = p.g.C[k - 1], R = p.g.R[k], C = p.g.C[k];
-        need = std::max(need, p.B * R * (fb_tiled_ok(p.B, R0, C0, tp) ? C : C0));
-        if (!fb_tiled_ok(p.B, 2 * R, 2 * C, tp)) need = std::max(need, p.B * R * 2 * C);
+        need = std::max(need, p.B * R * (lvl_tiled(p, p.B, R0, C0, tp) ? C : C0));
+        if (!lvl_tiled(p, p.B, 2 * R, 2 * C, tp)) need = std::max(need, p.B * R * 2 * C);
         if (k >= 2) need = std::max(need, p.B * 4 * R * C);
     }
     return (size_t)need;
@@ -380,7 +392,7 @@ void forward_chains(const std::vector<Chain>& cs, const Taps& tp, hipStream_t s,
             if (p.L < k) continue;
             float *tL = cs[j].T[0], *tH = cs[j].T[1], *tA = cs[j].T[2];
             const int64_t R0 = p.g.R[k - 1], C0 = p.g.C[k - 1];
-            if (fb_tiled_ok(p.B, R0, C0, tp)) {
+            if (lvl_tiled(p, p.B, R0, C0, tp)) {
                 float* an = (cur[j] == tA) ? tL : tA;
                 items.push_back(FwdItem{cur[j], p.B, R0, C0, an, cs[j].P, p.g.PR, p.g.PC, p.g.offR[k], p.g.offC[k],
                                         k == p.L});
@@ -426,7 +438,7 @@ void inverse_chains(const std::vector<Chain>& cs, const Taps& tp, hipStream_t s)
             const bool final = k == 1;
             const int64_t oH = final ? p.H : 2 * R, oW = final ? p.W : 2 * C;
             unsigned long long* zc = final ? cs[j].zc : nullptr;
-            if (fb_tiled_ok(p.B, 2 * R, 2 * C, tp)) {
+            if (lvl_tiled(p, p.B, 2 * R, 2 * C, tp)) {
                 float* y = final ? cs[j].out : ((cur[j] == tA) ? tL : tA);
                 items.push_back(InvItem{cur[j], a_bs, lda, fromP, cs[j].P, p.g.PR, p.g.PC, p.g.offR[k], p.g.offC[k],
                                         p.B, R, C, cs[j].thr, y, oH, oW, zc});
@@ -1196,6 +1208,168 @@ int wtp_count_small_f32(const float* x, int64_t n, float thr, unsigned long long
     if (hipMemsetAsync(count_dev, 0, sizeof(unsigned long long), s) != hipSuccess)
         return fail(WTP_EHIP, -1, "hipMemsetAsync failed");
     if (n > 0) launch_count_small(x, n, thr, count_dev, s);
+    return check_launch();
+}
+
+/* ------------------------------------------- the absolute-threshold method --- */
+/* dwt_pruning_NoEntropy.py:29-60.  Workspace: [the float32 threshold, one word on a line of its
+ * own | one chain region: a packed array and three level temps, sized for the largest chain
+ * tensor -- the chain tensors run one after another on the stream and share it]. */
+struct AbsPlan {
+    std::vector<TPlan> ps;
+    std::vector<int> path;
+    std::vector<int> nl_log2; /* tiny: lanes a wave uses */
+    size_t p_bytes = 0, t_bytes = 0, total = 0;
+};
+
+static int plan_abs(const wtp_tensor* ts, int n, int wid, int level, bool check_ptrs, AbsPlan& a) {
+    a.ps.assign(n, TPlan());
+    a.path.assign(n, WTP_ABS_PATH_MASK);
+    a.nl_log2.assign(n, 0);
+    const Taps tp = (wid >= 0 && wid < WT_NUM_WAVELETS) ? make_taps(wid) : Taps{};
+    for (int t = 0; t < n; ++t) {
+        const wtp_tensor& x = ts[t];
+        TPlan& p = a.ps[t];
+        if (x.ndim < 0 || x.ndim > WTP_MAX_DIMS) return fail(WTP_EARG, t, "tensor %d: ndim %d unsupported", t, x.ndim);
+        p.ndim = x.ndim;
+        p.numel = 1;
+        for (int d = 0; d < x.ndim; ++d) {
+            if (x.shape[d] < 0) return fail(WTP_EARG, t, "tensor %d: negative dimension", t);
+            p.numel *= x.shape[d];
+        }
+        if (check_ptrs && p.numel > 0 && (!x.in || !x.out)) return fail(WTP_EARG, t, "tensor %d: null pointer", t);
+        p.strict = true;
+        if (x.ndim < 2) { /* :35-38 -- a plain mask, no wavelet lookup, no level */
+            p.pop = p.numel;
+            continue;
+        }
+        if (wid < 0 || wid >= WT_NUM_WAVELETS)
+            return fail(WTP_EBADWAVELET, t, "Unknown wavelet name, check wavelist() for the list of available builtin wavelets.");
+        if (level < 0) return fail(WTP_EBADLEVEL, t, "Level value of %d is too low . Minimum level is 0.", level);
+        if (level > 32) return fail(WTP_EARG, t, "tensor %d: level %d unsupported", t, level);
+        if (p.numel == 0) return fail(WTP_EARG, t, "tensor %d: empty tensor with ndim >= 2", t);
+        p.H = x.shape[x.ndim - 2];
+        p.W = x.shape[x.ndim - 1];
+        p.B = p.numel / (p.H * p.W);
+        p.L = level;
+        p.dwt = level > 0;
+        wt_geom(p.H, p.W, p.L, &p.g);
+        p.pop = p.B * p.g.PR * p.g.PC;
+        int64_t nc = p.g.R[p.L] * p.g.C[p.L];
+        for (int k = 1; k <= p.L; ++k) nc += 3 * p.g.R[k] * p.g.C[k];
+        p.tight = !p.dwt || nc == p.g.PR * p.g.PC;
+        const int lg = p.B <= (int64_t)INT32_MAX ? abs_lanes_log2(p.H, p.W, p.L) : -1;
+        if (lg >= 0) {
+            a.path[t] = WTP_ABS_PATH_TINY;
+            a.nl_log2[t] = lg;
+            continue;
+        }
+        if (!p.dwt) continue;
+        a.path[t] = WTP_ABS_PATH_CHAIN;
+        p.t_elems = temp_elems(p, tp);
+        a.p_bytes = std::max(a.p_bytes, align_up((size_t)p.pop * sizeof(float)));
+        a.t_bytes = std::max(a.t_bytes, align_up(p.t_elems * sizeof(float)));
+    }
+    a.total = ALIGN + a.p_bytes + 3 * a.t_bytes;
+    return WTP_OK;
+}
+
+size_t wtp_abs_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level) {
+    if (ntensors < 0 || (ntensors > 0 && !tensors)) return 0;
+    AbsPlan a;
+    if (plan_abs(tensors, ntensors, wavelet_id, level, false, a) != WTP_OK) return 0;
+    return a.total;
+}
+
+int wtp_prune_abs_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double threshold, void* ws,
+                      size_t ws_bytes, wtp_abs_result* results, wtp_stream_t stream) {
+    g_err.clear();
+    g_err_tensor = -1;
+    if (ntensors < 0 || (ntensors > 0 && (!tensors || !results))) return fail(WTP_EARG, -1, "bad arguments");
+    if (ntensors == 0) return WTP_OK;
+    AbsPlan a;
+    int rc = plan_abs(tensors, ntensors, wavelet_id, level, true, a);
+    if (rc != WTP_OK) return rc;
+    if (!ws || ws_bytes < a.total)
+        return fail(WTP_EWORKSPACE, -1, "workspace too small: need %zu bytes, got %zu", a.total, ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const Taps tp = (wavelet_id >= 0 && wavelet_id < WT_NUM_WAVELETS) ? make_taps(wavelet_id) : Taps{};
+    /* np.abs(a_f32) < python_float compares in float32 with the threshold rounded to float32 */
+    const float thr32 = (float)threshold;
+    uint32_t thr_bits;
+    memcpy(&thr_bits, &thr32, 4);
+    float* thr_dev = reinterpret_cast<float*>(ws);
+    bool any_other = false;
+    for (int t = 0; t < ntensors; ++t) any_other = any_other || (a.path[t] != WTP_ABS_PATH_TINY && a.ps[t].numel > 0);
+    /* the counts are accumulated: every record starts from zero (an empty tensor's stays so); the
+     * existing kernels read the threshold from device memory: the same launch sets that word */
+    launch_abs_init(results, ntensors, any_other ? thr_dev : nullptr, thr_bits, s);
+    /* 1. every tiny-image tensor of the call in one launch (ABS_MAX_SEG tensors per kernel argument) */
+    {
+        AbsTable tab;
+        auto reset = [&]() {
+            memset(&tab, 0, offsetof(AbsTable, tp));
+            tab.thr_bits = thr_bits;
+        };
+        reset();
+        tab.tp = tp;
+        for (int t = 0; t <= ntensors; ++t) {
+            const bool flush = t == ntensors || (tab.nseg == ABS_MAX_SEG) ||
+                               (t < ntensors && a.path[t] == WTP_ABS_PATH_TINY &&
+                                (int64_t)tab.nwave + ((a.ps[t].B + (1 << a.nl_log2[t]) - 1) >> a.nl_log2[t]) > (int64_t)INT32_MAX);
+            if (flush && tab.nseg) {
+                launch_abs_tiny(tab, results, s);
+                reset();
+            }
+            if (t == ntensors || a.path[t] != WTP_ABS_PATH_TINY) continue;
+            const TPlan& p = a.ps[t];
+            AbsSeg& sg = tab.s[tab.nseg];
+            sg.in = tensors[t].in;
+            sg.out = tensors[t].out;
+            sg.B = (int32_t)p.B;
+            sg.H = (uint8_t)p.H;
+            sg.W = (uint8_t)p.W;
+            sg.L = (uint8_t)p.L;
+            sg.nl_log2 = (uint8_t)a.nl_log2[t];
+            sg.res = t;
+            tab.wave_begin[tab.nseg++] = tab.nwave;
+            tab.nwave += (int32_t)((p.B + (1 << a.nl_log2[t]) - 1) >> a.nl_log2[t]);
+        }
+    }
+    /* 2. the others, one after another: count_nonzero(in) before out is written (in place),
+     * the transform or the plain mask, count_nonzero(out) */
+    float* P = reinterpret_cast<float*>(wsb(ws, ALIGN));
+    for (int t = 0; t < ntensors; ++t) {
+        const TPlan& p = a.ps[t];
+        if (a.path[t] == WTP_ABS_PATH_TINY || p.numel == 0) continue;
+        wtp_abs_result init;
+        memset(&init, 0, sizeof init);
+        init.numel = p.numel;
+        init.coeff_numel = p.pop;
+        init.thr32_bits = thr_bits;
+        init.level = p.ndim >= 2 ? p.L : 0;
+        init.path = a.path[t];
+        launch_abs_count(tensors[t].in, p.numel, reinterpret_cast<unsigned long long*>(&results[t].nonzero_in),
+                         results + t, init, s);
+        if (a.path[t] == WTP_ABS_PATH_MASK) {
+            launch_copy_threshold(tensors[t].in, tensors[t].out, p.numel, thr_dev, nullptr, s);
+        } else {
+            Chain c;
+            c.p = &p;
+            c.in = tensors[t].in;
+            c.out = tensors[t].out;
+            c.P = P;
+            for (int i = 0; i < 3; ++i) c.T[i] = reinterpret_cast<float*>(wsb(ws, ALIGN + a.p_bytes + i * a.t_bytes));
+            c.thr = thr_dev;
+            c.zc = nullptr;
+            if (!p.tight) launch_abs_zero(P, p.pop, s);
+            const std::vector<Chain> cs{c};
+            forward_chains(cs, tp, s);
+            inverse_chains(cs, tp, s);
+        }
+        launch_abs_count(tensors[t].out, p.numel, reinterpret_cast<unsigned long long*>(&results[t].nonzero_out),
+                         nullptr, init, s);
+    }
     return check_launch();
 }
 

@@ -7,6 +7,7 @@
 
 #include "../../include/wtprune.h"
 #include "wt_dwt_core.h"
+#include "wt_abs_core.h"
 
 #pragma clang fp contract(off)
 
@@ -429,6 +430,36 @@ struct RandTable {
 };
 void launch_random_prune(const RandTable& t, wtp_result* res, hipStream_t s);
 void launch_count_small(const float* x, int64_t n, float thr, unsigned long long* count, hipStream_t s);
+/* ---- the absolute-threshold method (abs.hip, wtp_prune_abs_f32) ----
+ * k_abs_tiny: one wave per workgroup and per NL images of one tensor, word s of image i at
+ * lds[s * NL + i]; NL = 64 unless an image's areas (abs_tiny_words) need more than the wave's
+ * ABS_WAVE_WORDS / 64, then the next power of two that fits (the other lanes idle). */
+constexpr int ABS_MAX_SEG = 64;        /* tensors per k_abs_tiny launch (the table is its kernel argument) */
+constexpr int ABS_THREADS = 64;
+/* ABS_SIDE_MAX, ABS_TAP_WORDS, ABS_WAVE_WORDS and the lane choice abs_lanes_log2: wt_abs_core.h */
+constexpr int ABS_COUNT_THREADS = 256;
+struct AbsSeg {
+    const float* in;
+    float* out;
+    int32_t B;                 /* images */
+    uint8_t H, W, L, nl_log2;
+    int32_t res;               /* record index */
+    int32_t pad;
+};
+struct AbsTable {
+    int32_t nseg, nwave;
+    uint32_t thr_bits;         /* float32(threshold) */
+    int32_t pad;
+    int32_t wave_begin[ABS_MAX_SEG]; /* first wave (= workgroup) of every segment */
+    AbsSeg s[ABS_MAX_SEG];
+    Taps tp;
+};
+static_assert(sizeof(AbsTable) + 8 <= 4096, "k_abs_tiny's kernel argument");
+void launch_abs_init(wtp_abs_result* res, int n, float* thr_word, uint32_t thr_bits, hipStream_t s);
+void launch_abs_zero(float* p, int64_t n, hipStream_t s);
+void launch_abs_tiny(const AbsTable& t, wtp_abs_result* res, hipStream_t s);
+void launch_abs_count(const float* x, int64_t n, unsigned long long* dst, wtp_abs_result* rec,
+                      const wtp_abs_result& init, hipStream_t s);
 /* 1-D flattened mode (one line per tensor) */
 void launch_dwt1_level(const float* x, int64_t N, const Taps& tp, float* a, float* d, hipStream_t s);
 void launch_idwt1_level(const float* a, int a_thr, const float* d, int64_t N, const Taps& tp, const float* thr,

@@ -24,18 +24,21 @@ def wavelet_id(name):
     return N.lib().wtp_wavelet_id(str(name).encode()) if isinstance(name, str) else -1
 
 
-def workspace(device, nbytes, stream=None):
-    """Grow-only, zero-initialised workspace per (device, stream): the selection, barrier and
+def workspace(device, nbytes, stream=None, kind=None):
+    """Grow-only, zero-initialised workspace per (device, stream, kind): the selection, barrier and
     parity state of a call live in it, so calls on distinct streams need distinct workspaces
     (include/wtprune.h).  The library keeps it clean between calls on its stream.  Each stream
     ever used keeps its workspace (at the largest size it needed: a cfg5-sized call holds the
-    packed coefficients of its images) until release_workspaces() drops it."""
+    packed coefficients of its images) until release_workspaces() drops it.  kind=None is the
+    workspace of the selection entries, whose state the library keeps clean; an entry that uses its
+    workspace as plain scratch (launch_abs: kind="abs") gets one of its own, so it never writes over
+    that state."""
     device = torch.device(device)
     if device.index is None:
         device = torch.device(device.type, torch.cuda.current_device())
     if stream is None:
         stream = torch.cuda.current_stream(device)
-    key = (device.index, stream.cuda_stream)
+    key = (device.index, stream.cuda_stream) if kind is None else (device.index, stream.cuda_stream, kind)
     ws = _workspaces.get(key)
     if ws is None or ws.numel() < nbytes:
         if torch.cuda.is_current_stream_capturing():
@@ -283,6 +286,67 @@ def prune(tensors, wavelet, level, pct, outs=None, carry_level=True, flatten=Fal
             merged[g] = res2.view(len(g), N.RESULT_BYTES)
         res = merged.view(-1)
     return outs, decode(res, n)
+
+
+ABS_RESULT_DTYPE = np.dtype([("numel", "<i8"), ("nonzero_in", "<i8"), ("nonzero_out", "<i8"), ("coeff_numel", "<i8"),
+                             ("thr32_bits", "<u4"), ("level", "<i4"), ("path", "<i4"), ("reserved", "<i4")])
+assert ABS_RESULT_DTYPE.itemsize == N.ABS_RESULT_BYTES
+ABS_PATH_MASK, ABS_PATH_TINY, ABS_PATH_CHAIN = 0, 1, 2  # include/wtprune.h
+
+
+def launch_abs(tensors, wavelet, level, threshold, outs=None, stream=None):
+    """Enqueue the absolute-threshold method (dwt_pruning_NoEntropy.py:29-60, wtp_prune_abs_f32) for
+    `tensors` (CUDA float32) on `stream` (default: the current stream): the wavelet transform at
+    the requested level (no clamp), every packed coefficient with |c| < float32(threshold) set
+    to zero, the inverse, the crop; ndim < 2 tensors are masked as they are.  Returns (outs,
+    results_dev) without synchronising; results_dev is a uint8 CUDA tensor of len(tensors)
+    wtp_abs_result records (decode_abs).  outs may be the inputs (in place)."""
+    check_tensors(tensors)
+    tensors = [x.contiguous() for x in tensors]
+    if outs is None:
+        outs = [torch.empty_like(x) for x in tensors]
+    else:
+        check_outs(tensors, outs)
+    n = len(tensors)
+    if n == 0:
+        return outs, None
+    device = tensors[0].device
+    L = N.lib()
+    wid = wavelet_id(wavelet)
+    desc = _as_desc(tensors, outs)
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    nbytes = L.wtp_abs_workspace_size(desc, n, wid, int(level))
+    # scratch of this entry alone: never the selection entries' workspace (include/wtprune.h)
+    ws = workspace(device, nbytes if nbytes else 256, stream, kind="abs")
+    with torch.cuda.stream(stream):
+        res = torch.empty(n * N.ABS_RESULT_BYTES, dtype=torch.uint8, device=device)
+    rc = L.wtp_prune_abs_f32(desc, n, wid, int(level), float(threshold), ws.data_ptr(), ws.numel(), res.data_ptr(),
+                             ctypes.c_void_p(stream.cuda_stream))
+    if rc != N.WTP_OK:
+        raise_for(rc, tensors, wavelet)
+    return outs, res
+
+
+def decode_abs(results_dev, n):
+    """Host copies of n wtp_abs_result records as dicts (waits for the stream that wrote them)."""
+    host = results_dev.cpu().numpy().view(ABS_RESULT_DTYPE)[:n]
+    out = []
+    for r in host:
+        d = {k: r[k].item() for k in ABS_RESULT_DTYPE.names if k != "reserved"}
+        d["thr32"] = float(np.array(d["thr32_bits"], np.uint32).view(np.float32))
+        d["pruned"] = d["nonzero_in"] - d["nonzero_out"]
+        out.append(d)
+    return out
+
+
+def prune_abs(tensors, wavelet, level, threshold, outs=None):
+    """launch_abs() + wait + decoded per-tensor records (numel, nonzero_in, nonzero_out, pruned,
+    coeff_numel, thr32, level, path)."""
+    outs, res = launch_abs(tensors, wavelet, level, threshold, outs=outs)
+    if res is None:
+        return outs, []
+    return outs, decode_abs(res, len(tensors))
 
 
 def min_prune(tensors, fraction, outs=None):
