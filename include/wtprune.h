@@ -219,12 +219,31 @@ int wtp_set_resident(int mode);
 int wtp_resident_capacity(void); /* 0 if the current device cannot host the resident launch */
 /* Bound (microseconds) of every wait inside the resident launch; returns the previous bound.  A
  * launch whose workgroups were not all resident at once times out there and stores NOTHING for
- * the tensors concerned (inputs and outputs untouched): their records read path == 99
+ * the tensors concerned (inputs untouched; outputs untouched too, except as wtp_set_resident_early
+ * says for out-of-place tensors): their records read path == 99
  * (WTP_PATH_FAULT), and the caller re-runs exactly those tensors with wtp_set_resident(0).
  * Default 2000 (about 75x a full ResNet-18 resident launch), at most 40000000 (larger values are clamped: the bound is kept in 32-bit
  * ticks of the 100 MHz wall clock); tests lower it to force the fault path. */
 unsigned wtp_set_resident_timeout_us(unsigned us);
 #define WTP_PATH_FAULT 99
+/* Early stores of the resident launch.  A tensor of more than one workgroup (49152 weights) has
+ * its percentile selected by a workgroup of its own; as soon as that selector knows the key range
+ * [lo, hi] holding the threshold (1/1024 of the sample window) it publishes it, and the tensor's
+ * workgroups store at once every 64-lane float4 store none of whose weights has |w| in [lo, hi]
+ * (|w| < lo: 0, |w| > hi: kept -- exact, not speculative); the few per cent left wait for the
+ * threshold.  Identical results.  Out of place only: a tensor pruned in place keeps "all of it
+ * stored or none".  Out of place, a tensor whose wait times out AFTER its range was published
+ * may be left with its OUTPUT partly written (its input is never touched): its record still reads
+ * path == 99 and the re-run overwrites the whole output.  Mode 1 (default) on, 0 off, 2 on with
+ * the stores counted (measurement: two atomic adds per wave); any other value is rejected
+ * (WTP_EARG).  Returns the previous mode (process-wide).  The environment variable
+ * WTP_RESIDENT_EARLY (0 / 1 / 2) sets the mode a process starts with. */
+int wtp_set_resident_early(int mode);
+/* Mode 2's counters of `workspace` (the one passed to the prune calls): wave-wide float4 stores
+ * issued on the range / held back for the threshold since the last read; waits for `stream`,
+ * reads them and clears them. */
+int wtp_resident_early_counts(void* workspace, wtp_stream_t stream, unsigned long long* early,
+                              unsigned long long* deferred);
 /* A call with more than one launch group (24 tensors) of wavelet-transformed tensors runs each
  * group's percentile selection on a side stream of the library's (one per device and caller
  * stream, non-blocking, created on first use), overlapping the next group's forward transform;

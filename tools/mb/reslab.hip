@@ -4,7 +4,7 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off reslab.hip -o reslab
 #include <hip/hip_runtime.h>
 #define NWG 256
-__device__ unsigned long long g_rprobe[NWG][20];
+__device__ unsigned long long g_rprobe[NWG][24]; /* 0-11 phases, 12-17 window, 19 tag, 20 bound seen, 21 early stores issued */
 __device__ unsigned long long g_cyc[NWG][2];
 __device__ unsigned long long g_sprobe[NWG][16];
 #ifndef RESLAB_NOPROBE
@@ -19,6 +19,7 @@ __device__ unsigned long long g_sprobe[NWG][16];
 #include "kernels.hip"  /* -I wavelettransforms_amd/csrc (or a variant copy) */
 #include "filterbank.hip"  /* -I wavelettransforms_amd/csrc (or a variant copy) */
 #include "small.hip"  /* -I wavelettransforms_amd/csrc (or a variant copy) */
+#include "abs.hip"
 #include "api.hip"  /* -I wavelettransforms_amd/csrc (or a variant copy) */
 #include <cstdio>
 #include <vector>
@@ -65,7 +66,7 @@ int main(int argc, char** argv) {
     for (int i = 0; i < 5; ++i) if (wtp_prune_layers_f32(ts.data(), 20, wid, 5, 50.0, ws, wsb, res, 0)) { printf("err %s\n", wtp_last_error()); return 1; }
     CK(hipDeviceSynchronize());
     std::vector<float> tms;
-    static unsigned long long pr[NWG][20];
+    static unsigned long long pr[NWG][24];
     std::vector<std::vector<double>> ph(18), sel(15), phg[2];
     phg[0].resize(18); phg[1].resize(18);
     const size_t FL = (size_t)512 << 20;
@@ -115,10 +116,13 @@ int main(int argc, char** argv) {
             int nb = 0; for (int t = 0; t < 20; ++t) { int64_t n = 1; for (int d = 0; d < 4; ++d) n *= shapes[t][d]; nb += (int)((n + RES_CHUNK - 1) / RES_CHUNK); }
             unsigned long long t0 = ~0ull;
             for (int i = 0; i < nb; ++i) t0 = std::min(t0, pr[i][0]);
-            fprintf(f, "wg,late,start,window,counted,hist-pub,B1-arrive,B1-pass,selected,stored,sampled,sorted,issued,published\n");
+            fprintf(f, "wg,late,start,window,counted,hist-pub,B1-arrive,B1-pass,selected,stored,sampled,sorted,issued,published,bound-seen,early-issued\n");
             for (int i = 0; i < nb; ++i) {
                 fprintf(f, "%d,%d", i, (int)((pr[i][19] >> 4) & 1));
                 for (int p = 0; p < 12; ++p) fprintf(f, ",%.2f", (double)(pr[i][p] - t0) / 100.0);
+                /* the early-store hops: -1 where the workgroup did not take them in this launch */
+                for (int p = 20; p < 22; ++p)
+                    fprintf(f, ",%.2f", pr[i][p] >= t0 && pr[i][p] <= pr[i][7] ? (double)(pr[i][p] - t0) / 100.0 : -1.0);
                 fprintf(f, "\n");
             }
             fclose(f);
@@ -166,8 +170,27 @@ int main(int argc, char** argv) {
         auto us = [&](unsigned long long x) { return x >= t0 && x - t0 < 100000000ull ? (double)(x - t0) / 100.0 : -1.0; };
         for (int i = nb; i < NWG; ++i) {
             if (pr[i][0] < t0 || pr[i][0] - t0 > 100000000ull) continue;
-            printf("  selector %3d: start %6.2f  window %6.2f  B1-pass %6.2f  counters %6.2f  B2-pass %6.2f  staged %6.2f  ranks %6.2f  granule %6.2f\n",
-                   i, us(pr[i][0]), us(pr[i][1]), us(pr[i][5]), us(sp[i][1]), us(sp[i][4]), us(sp[i][5]), us(sp[i][6]), us(pr[i][6]));
+            printf("  selector %3d: start %6.2f  window %6.2f  B1-pass %6.2f  counters %6.2f  bound %6.2f  B2-pass %6.2f  staged %6.2f  ranks %6.2f  granule %6.2f\n",
+                   i, us(pr[i][0]), us(pr[i][1]), us(pr[i][5]), us(sp[i][1]), us(sp[i][3]), us(sp[i][4]), us(sp[i][5]), us(sp[i][6]), us(pr[i][6]));
+        }
+    }
+    {   /* the early-store hops of the last rep's data workgroups that took them */
+        int nb = 0; for (int t = 0; t < 20; ++t) { int64_t n = 1; for (int d = 0; d < 4; ++d) n *= shapes[t][d]; nb += (int)((n + RES_CHUNK - 1) / RES_CHUNK); }
+        unsigned long long t0 = ~0ull;
+        for (int i = 0; i < nb; ++i) t0 = std::min(t0, pr[i][0]);
+        std::vector<double> bs, ei, fg;
+        for (int i = 0; i < nb; ++i)
+            if (pr[i][20] >= t0 && pr[i][20] <= pr[i][7]) {
+                bs.push_back((double)(pr[i][20] - t0) / 100.0);
+                ei.push_back((double)(pr[i][21] - t0) / 100.0);
+                fg.push_back((double)(pr[i][6] - t0) / 100.0);
+            }
+        if (!bs.empty()) {
+            std::sort(bs.begin(), bs.end()); std::sort(ei.begin(), ei.end()); std::sort(fg.begin(), fg.end());
+            printf("  early stores: %zu of %d data workgroups; bound seen median %.2f (first %.2f, last %.2f)  issued median %.2f  threshold seen median %.2f us\n",
+                   bs.size(), nb, bs[bs.size() / 2], bs[0], bs.back(), ei[ei.size() / 2], fg[fg.size() / 2]);
+        } else {
+            printf("  early stores: none taken\n");
         }
     }
     const char* snames[15] = {"-", "counters", "buckets", "B2-wait", "B2-pass", "staged", "ranks", "-", "-", "-", "-", "-", "-", "-", "-"};

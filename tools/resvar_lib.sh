@@ -12,7 +12,7 @@ build_one() {
     if cmp -s $T/o $T/w/csrc/$f; then echo "variant $v: '$e' changed nothing in $f" >&2; exit 1; fi
   done < $R/tools/resvar/$v.sed
   (cd $T/w/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -I. -I../../include \
-    -o $R/tools/ab/libwtprune_$v.so kernels.hip filterbank.hip small.hip api.hip)
+    -o $R/tools/ab/libwtprune_$v.so *.hip)
   rm -rf $T
   echo "built tools/ab/libwtprune_$v.so"
 }

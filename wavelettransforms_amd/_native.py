@@ -95,6 +95,9 @@ def lib():
             "wtp_resident_capacity": ([], i32),
             "wtp_set_resident_timeout_us": ([ctypes.c_uint], ctypes.c_uint),
             "wtp_set_kernel_stamps": ([vp], i32),
+            "wtp_set_resident_early": ([i32], i32),
+            "wtp_resident_early_counts": ([vp, vp, ctypes.POINTER(ctypes.c_ulonglong),
+                                           ctypes.POINTER(ctypes.c_ulonglong)], i32),
             "wtp_last_error": ([], ctypes.c_char_p),
             "wtp_last_error_tensor": ([], i32),
         }

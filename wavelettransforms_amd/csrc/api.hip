@@ -664,6 +664,22 @@ int wtp_set_fused_select(int mode) {
     return g_fused.exchange(mode);
 }
 unsigned wtp_set_resident_timeout_us(unsigned us) { return set_resident_timeout_us(us); }
+int wtp_set_resident_early(int mode) {
+    if (mode < 0 || mode > 2) return fail(WTP_EARG, -1, "bad resident early-store mode %d", mode);
+    return set_resident_early(mode);
+}
+int wtp_resident_early_counts(void* ws, wtp_stream_t stream, unsigned long long* early, unsigned long long* deferred) {
+    if (!ws || !early || !deferred) return fail(WTP_EARG, -1, "bad early-count request");
+    SelHeader* head = reinterpret_cast<SelHeader*>(ws); /* Layout::sel = 0 */
+    uint32_t c[2] = {0u, 0u};
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemcpyAsync(c, &head->early_ws, sizeof(c), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemsetAsync(&head->early_ws, 0, sizeof(c), s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return fail(WTP_EHIP, -1, "reading the early-store counters failed");
+    *early = c[0];
+    *deferred = c[1];
+    return WTP_OK;
+}
 int wtp_set_kernel_stamps(unsigned long long* stamps_dev) {
     set_kernel_stamps(stamps_dev);
     return WTP_OK;

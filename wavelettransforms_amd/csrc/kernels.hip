@@ -1500,7 +1500,9 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_mask_select(SegTable t, cons
  *       shard's arrival counter (blockIdx % 8), wave 0 polls all shards with sc1 loads
  *   P2  every workgroup resolves its segment's threshold (select_body over sc1 loads); the
  *       segment's first workgroup publishes the record and the exact zero count
- *   P3  out = where(|x| < thr, 0, x) from registers
+ *   P3  out = where(|x| < thr, 0, x) from registers; a shared segment's workgroups (out of
+ *       place) store every wave-wide float4 already decided by the ranks' bucket as soon as their
+ *       selector publishes it, ahead of the threshold (the early stores, above res_body)
  * A segment whose window missed is re-scanned from memory (full radix select); when its input is
  * also its output (in place) its workgroups meet at a segment-wide barrier before any writes.
  * Every wait is bounded (RES_TIMEOUT of the 100 MHz wall clock): a grid that is not co-resident
@@ -1648,6 +1650,85 @@ __device__ __forceinline__ void res_final(const float4 (&v)[RES_IT], float thr, 
         const unsigned long long tot = block_sum_u64<CT>(z) - (unsigned long long)(RES_CHUNK - len);
         if (tid == 0 && tot) atomicAdd((unsigned long long*)&res[sd.res].zero_count, tot);
     }
+    WTP_RPROBE(7);
+}
+
+/* ---- early stores (a remote segment's data workgroups, out of place) ----
+ * The selector publishes the bound granule {lo, hi} -- the key range of the ranks' buckets, which
+ * holds both order statistics and so the threshold -- three hops (barrier 2, offsets, keys + LDS
+ * select) before the threshold granule.  Every key outside [lo, hi] is decided by it exactly:
+ * key < lo <= ka gives |x| < thr (0), key > hi >= kb gives |x| > thr (kept).  A wave-wide float4
+ * store (64 lanes x 16 B) none of whose 256 keys lies in [lo, hi] goes out whole on the bound;
+ * the others (a few per cent: [lo, hi] is 1/1024 of the window) are held back for the threshold,
+ * one bit each in a wave-uniform mask.  Nothing is written twice, except after RES_GR_ALL. */
+
+/* one poll of a slot's granule pair {thr_gr, bnd_gr}: ONE aligned 16-byte sc1 load (each 8-byte
+ * half is written whole by one store or compare-and-swap) */
+__device__ __forceinline__ void res_poll_pair(const SelState* st, unsigned long long* thr, unsigned long long* bnd) {
+    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+    u4v x;
+    const unsigned long long* p = &st->thr_gr;
+    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(x) : "v"(p) : "memory");
+    *thr = ((unsigned long long)x.y << 32) | x.x;
+    *bnd = ((unsigned long long)x.w << 32) | x.z;
+}
+
+/* float4 slot `it` of the thread, in res_final's store forms */
+template <bool FULL>
+__device__ __forceinline__ void res_store_slot(const float4& y, float* qo, __amdgpu_buffer_rsrc_t rr, int it, int len,
+                                               bool al) {
+    const int j = it * RES_THREADS + (int)threadIdx.x;
+    if (FULL) {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const f4v yv = {y.x, y.y, y.z, y.w};
+        __builtin_nontemporal_store(yv, reinterpret_cast<f4v*>(qo) + j);
+    } else {
+        store4_tail(y, qo, rr, j, len, al);
+    }
+}
+
+/* the wave's decided float4 stores on the bound [lo, hi]; returns the wave-uniform mask of the
+ * slots held back (bit it: some lane of the wave has a key of slot it inside [lo, hi]).
+ * STORE = false: classification only (the polling wave when RES_EARLY_POLL_STORES is off). */
+template <bool FULL, bool STORE>
+__device__ __forceinline__ uint32_t res_early_stores(const float4 (&v)[RES_IT], uint32_t lo, uint32_t hi,
+                                                     const SegDesc& sd, int64_t base, int len, bool al) {
+    float* qo = sd.out + base;
+    const __amdgpu_buffer_rsrc_t rr = ragged_rsrc(qo, FULL ? 0 : len);
+    const uint32_t w = hi - lo;
+    uint32_t pend = 0; /* wave-uniform: a scalar register */
+#pragma unroll
+    for (int it = 0; it < RES_IT; ++it) {
+        uint32_t k4[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) k4[c] = abs_key(f4_get(v[it], c));
+        const bool in = (k4[0] - lo <= w) | (k4[1] - lo <= w) | (k4[2] - lo <= w) | (k4[3] - lo <= w);
+        if (__ballot(in) != 0ull) { /* uniform */
+            pend |= 1u << it;
+        } else if (STORE) {
+            const float4 y = make_float4(k4[0] < lo ? 0.0f : v[it].x, k4[1] < lo ? 0.0f : v[it].y,
+                                         k4[2] < lo ? 0.0f : v[it].z, k4[3] < lo ? 0.0f : v[it].w);
+            res_store_slot<FULL>(y, qo, rr, it, len, al);
+        }
+    }
+    return pend;
+}
+
+/* after the threshold granule: the slots of `pend` with the threshold itself (finite: the bound
+ * is published only for a segment without NaN and with finite rank buckets) */
+template <bool FULL>
+__device__ __forceinline__ void res_pending_stores(const float4 (&v)[RES_IT], uint32_t pend, float thr,
+                                                   const SegDesc& sd, int64_t base, int len, bool al) {
+    float* qo = sd.out + base;
+    const __amdgpu_buffer_rsrc_t rr = ragged_rsrc(qo, FULL ? 0 : len);
+    auto fin = [&](float xv) { return (fabsf(xv) < thr) ? 0.0f : xv; };
+    pend = __builtin_amdgcn_readfirstlane(pend); /* wave-uniform: scalar branches below */
+#pragma unroll
+    for (int it = 0; it < RES_IT; ++it)
+        if (pend & (1u << it)) { /* uniform */
+            const float4 y = make_float4(fin(v[it].x), fin(v[it].y), fin(v[it].z), fin(v[it].w));
+            res_store_slot<FULL>(y, qo, rr, it, len, al);
+        }
     WTP_RPROBE(7);
 }
 
@@ -1989,13 +2070,16 @@ __device__ __forceinline__ void res_body(const SegTable& t, const SegDesc& sd, S
          * word; the region is zero at the launch's start).  A wait that times out claims the
          * granule for FAULT by compare-and-swap, so every workgroup of the segment and the
          * selector agree: all store, or none does */
-        __shared__ unsigned long long s_gr;
+        __shared__ unsigned long long s_gr, s_bnd;
+        const bool early = t.res_early != 0; /* uniform over the grid (kernel argument) */
         if (wv == NW - 1 && lane == 0) {
             const uint64_t t0 = wall_ticks();
-            unsigned long long x;
+            unsigned long long x, b = 0ull;
             while (true) {
-                x = ldc<true>(reinterpret_cast<const unsigned long long*>(gr));
+                if (early) res_poll_pair(st, &x, &b);
+                else x = ldc<true>(reinterpret_cast<const unsigned long long*>(gr));
                 if (x) break;
+                if (b) break; /* the bound first: the decided stores go out now */
                 if (wall_ticks() - t0 >= tmo) {
                     const unsigned long long f = (unsigned long long)RES_GR_FAULT << 32;
                     const unsigned long long o = atomicCAS(reinterpret_cast<unsigned long long*>(gr), 0ull, f);
@@ -2005,9 +2089,59 @@ __device__ __forceinline__ void res_body(const SegTable& t, const SegDesc& sd, S
                 __builtin_amdgcn_s_sleep(2);
             }
             s_gr = x;
+            s_bnd = b;
         }
         __syncthreads();
-        const unsigned long long g = s_gr;
+        unsigned long long g = s_gr;
+        if (g == 0ull) {
+            /* ---- the bound granule came first: every wave stores its decided float4 now (the
+             * polling wave too: RES_EARLY_POLL_STORES) and keeps the rest for the threshold */
+            const unsigned long long bw = s_bnd;
+            const uint32_t lo = (uint32_t)bw, hi = (uint32_t)(bw >> 32) & ~RES_BND_VALID;
+            WTP_RPROBE(20); /* bound seen */
+            uint32_t pend;
+            if (wv == NW - 1 && !RES_EARLY_POLL_STORES) pend = res_early_stores<FULL, false>(v, lo, hi, sd, base, len, al);
+            else pend = res_early_stores<FULL, true>(v, lo, hi, sd, base, len, al);
+            WTP_RPROBE(21); /* early stores issued */
+            if (t.res_early == 2 && lane == 0) { /* measurement only */
+                const uint32_t nd = (uint32_t)__builtin_popcount(pend);
+                atomicAdd(&head->early_ws, (uint32_t)IT - nd);
+                if (nd) atomicAdd(&head->defer_ws, nd);
+            }
+            __syncthreads(); /* s_gr is read by every wave before it is rewritten */
+            if (wv == NW - 1 && lane == 0) {
+                const uint64_t t0 = wall_ticks();
+                unsigned long long x;
+                while (true) {
+                    x = ldc<true>(reinterpret_cast<const unsigned long long*>(gr));
+                    if (x) break;
+                    if (wall_ticks() - t0 >= tmo) {
+                        const unsigned long long f = (unsigned long long)RES_GR_FAULT << 32;
+                        const unsigned long long o = atomicCAS(reinterpret_cast<unsigned long long*>(gr), 0ull, f);
+                        x = o ? o : f;
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(2);
+                }
+                s_gr = x;
+            }
+            __syncthreads();
+            g = s_gr;
+            const uint32_t tag2 = (uint32_t)(g >> 32);
+            if (tag2 & RES_GR_FAULT) { /* out of place: the output stays partly written, the record says FAULT */
+                if (tid == 0) atomicMax(&res[sd.res].path, (int32_t)MODE_FAULT);
+                return;
+            }
+            const float thr2 = __uint_as_float((uint32_t)g);
+            WTP_RPROBE(6);
+            if ((tag2 & RES_GR_ALL) || thr2 != thr2) {
+                res_final<FULL>(v, thr2, sd, res, base, len, al); /* the selector left [lo, hi]: every float4 again */
+            } else {
+                if (wv == NW - 1 && !RES_EARLY_POLL_STORES) pend = (1u << IT) - 1u; /* the polling wave: all of its float4 */
+                res_pending_stores<FULL>(v, pend, thr2, sd, base, len, al);
+            }
+            return;
+        }
         const uint32_t tag = (uint32_t)(g >> 32);
         if (tag & RES_GR_FAULT) {
             if (tid == 0) atomicMax(&res[sd.res].path, (int32_t)MODE_FAULT);
@@ -2100,6 +2234,8 @@ __device__ __forceinline__ void res_body(const SegTable& t, const SegDesc& sd, S
     int m = 0;
     uint32_t* stage = raw; /* the window histogram is done with */
     const uint32_t* sel_keys = stage; /* the staged keys of the ranks' buckets */
+    bool bnd_pub = false;      /* the selector published the bound granule [blo, bhi] */
+    uint32_t blo = 0, bhi = 0;
     if (!full && (ca == 2 || cb == 2)) {
         const int ba = ca == 2 ? s_bk[0] : s_bk[1], bb = cb == 2 ? s_bk[1] : s_bk[0];
         before = ca == 2 ? s_bef[0] : s_bef[1];
@@ -2120,6 +2256,20 @@ __device__ __forceinline__ void res_body(const SegTable& t, const SegDesc& sd, S
         } else if (m > RES_SEL_MAX) {
             full = true; /* uniform over the segment: the same totals everywhere */
         } else {
+            /* ---- the bound granule: the ranks' buckets are named, so the threshold lies in
+             * [blo, bhi] -- published before barrier 2's wait, for the data workgroups' early
+             * stores.  Only where that range is certain to hold the threshold and a rewrite would
+             * be harmless: both ranks inside the window, no overflow, no NaN (mk), no inf in the
+             * rank buckets (the lerp stays finite), out of place; and only for a window closed on
+             * both sides (pct 0 and 100 open it below / above: no bound there). */
+            if (sel && t.res_early != 0 && ca == 2 && cb == 2 && mk <= 0x7F800000u && sd.out != sd.data && kl > 0u &&
+                kh != 0xFFFFFFFFu) {
+                blo = (uint32_t)((uint64_t)kl + ((uint64_t)ba << sh));
+                bhi = (uint32_t)min((uint64_t)kh, (uint64_t)kl + ((uint64_t)(bb + 1) << sh) - 1);
+                bnd_pub = bhi < 0x7F800000u; /* block-uniform */
+                if (bnd_pub && tid == 0)
+                    stc(&st->bnd_gr, ((unsigned long long)(bhi | RES_BND_VALID) << 32) | blo);
+            }
             /* ---- barrier 2: every region of the segment is published (its arrivals were made
              * before barrier 1's wait, so this wait is short) */
             WTP_PROBE(3);
@@ -2215,7 +2365,9 @@ __device__ __forceinline__ void res_body(const SegTable& t, const SegDesc& sd, S
         /* the threshold granule for the segment's workgroups, ahead of the record: {thr bits, tag},
          * claimed by compare-and-swap (a workgroup whose wait timed out may have claimed it for
          * FAULT) */
-        const uint32_t tag = RES_GR_OK | (path == MODE_FULL ? RES_GR_ALL : 0u);
+        /* RES_GR_ALL also where the ranks resolved outside a published bound (cannot happen with
+         * consistent totals; the rewrite keeps the output exact if it ever does) */
+        const uint32_t tag = RES_GR_OK | ((path == MODE_FULL || (bnd_pub && (ka < blo || kb > bhi))) ? RES_GR_ALL : 0u);
         const unsigned long long gv = ((unsigned long long)tag << 32) | __float_as_uint(thr);
         if (atomicCAS(reinterpret_cast<unsigned long long*>(gr), 0ull, gv) != 0ull)
             atomicMax(&res[sd.res].path, (int32_t)MODE_FAULT);
@@ -2776,6 +2928,26 @@ static std::atomic<uint32_t> g_res_timeout_us{RES_TIMEOUT_DEFAULT_US};
 uint32_t set_resident_timeout_us(uint32_t us) { return g_res_timeout_us.exchange(std::min(us, RES_TIMEOUT_MAX_US)); }
 static std::atomic<unsigned long long*> g_stamps{nullptr};
 void set_kernel_stamps(unsigned long long* dev) { g_stamps.store(dev); }
+/* early stores: on unless the environment says otherwise (WTP_RESIDENT_EARLY = 0 / 1 / 2, read
+ * once; wtp_set_resident_early overrides it) */
+static int env_resident_early() {
+    const char* e = getenv("WTP_RESIDENT_EARLY");
+    return (e && e[0] >= '0' && e[0] <= '2' && !e[1]) ? e[0] - '0' : 1;
+}
+static std::atomic<int> g_res_early{-1};
+int resident_early() {
+    int m = g_res_early.load(std::memory_order_relaxed);
+    if (m < 0) {
+        int want = env_resident_early();
+        if (g_res_early.compare_exchange_strong(m, want)) m = want;
+    }
+    return m;
+}
+int set_resident_early(int mode) {
+    const int prev = resident_early();
+    g_res_early.store(mode);
+    return prev;
+}
 uint32_t resident_timeout_us() { return g_res_timeout_us.load(std::memory_order_relaxed); }
 unsigned long long* kernel_stamps() { return g_stamps.load(std::memory_order_relaxed); }
 void launch_resident(const SegTable& t0, SelHeader* head, uint32_t* cand, wtp_result* res, float* thr_out,
@@ -2783,6 +2955,7 @@ void launch_resident(const SegTable& t0, SelHeader* head, uint32_t* cand, wtp_re
     SegTable t = t0;
     t.res_timeout = g_res_timeout_us.load(std::memory_order_relaxed) * 100u; /* 100 MHz wall clock */
     t.stamps = g_stamps.load(std::memory_order_relaxed);
+    t.res_early = resident_early();
     /* one selector workgroup per shared segment when they fit beside the chunks (one per CU):
      * the segment's select runs on a CU that holds no chunk */
     int nshared = 0;

@@ -3,6 +3,7 @@
 #define WTP_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/wtprune.h"
@@ -108,7 +109,7 @@ struct SegTable {
     int32_t nsel;      /* k_resident: selector workgroups after the nblk chunks (0: every segment selects for itself) */
     int32_t retry;     /* fused selection's retry launches: only segments whose record reads MODE_RETRY */
     uint32_t res_timeout; /* k_resident: bound of every wait, in ticks of the 100 MHz wall clock */
-    int32_t pad2;
+    int32_t res_early;    /* k_resident: early stores (wtp_set_resident_early): 0 off, 1 on, 2 on and counted */
     unsigned long long* stamps; /* k_resident: [0] min start, [1] max end (100 MHz ticks); null = off */
     int32_t blk_begin[SEG_PER_LAUNCH]; /* INT32_MAX past nseg: block -> segment in one scalar sweep */
     int32_t sel_seg[SEG_PER_LAUNCH];   /* k_resident: the segment of selector j */
@@ -131,9 +132,13 @@ struct alignas(128) SelState {
     unsigned long long seg_bar[NSHARD]; /* k_resident: [0] = workgroups of the segment past a full-scan select */
     uint32_t maxkey[NSHARD];          /* atomicMax (k_collect)                               */
     uint32_t overflow;                /* a block had more inside keys than it can stage     */
-    uint32_t pad0a;
-    unsigned long long thr_gr;        /* k_resident: the selector's threshold granule {thr bits, RES_GR_* tag} */
-    uint32_t pad0[20];
+    uint32_t pad0a[3];
+    /* k_resident: the selector's two granules, one aligned 16-byte pair (a data workgroup's poll
+     * reads both in one sc1 load); both are 0 until published (the idle-region clear) */
+    unsigned long long thr_gr;        /* the threshold granule {thr bits, RES_GR_* tag} */
+    unsigned long long bnd_gr;        /* the bound granule {lo, hi | RES_BND_VALID}: the threshold's key range
+                                       * (the ranks' buckets), known three hops before the threshold */
+    uint32_t pad0[16];
     uint32_t kl, kh;                  /* window (k_collect); kh = 0xFFFFFFFF: unbounded      */
     uint32_t shift;                   /* bucket of an inside key = (key - kl - 1) >> shift   */
     int32_t mode;                     /* MODE_* chosen by the select (diagnostics)           */
@@ -143,6 +148,9 @@ struct alignas(128) SelState {
     uint32_t sub[RES_NSUB];           /* keys per bucket (atomicAdd; k_collect uses <= NSUB_MAX) */
 };
 static_assert(sizeof(SelState) % 128 == 0 && sizeof(SelState) == 512 + 4 * RES_NSUB, "SelState layout");
+static_assert(offsetof(SelState, thr_gr) % 16 == 0 && offsetof(SelState, bnd_gr) == offsetof(SelState, thr_gr) + 8 &&
+                  offsetof(SelState, kl) == 384,
+              "SelState granule pair");
 
 /* The persistent head of a workspace: two SelState regions used alternately by successive
  * launch groups.  A group's k_collect accumulates into region `parity`, zeroes the other
@@ -152,7 +160,11 @@ static_assert(sizeof(SelState) % 128 == 0 && sizeof(SelState) == 512 + 4 * RES_N
 struct alignas(128) SelHeader {
     uint32_t parity;
     uint32_t done; /* k_collect blocks finished (last one flips parity and clears this) */
-    uint32_t pad[30];
+    /* k_resident with early stores counted (wtp_set_resident_early(2)): wave-wide float4 stores
+     * issued on the bound granule / held back for the threshold, summed over launches until
+     * wtp_resident_early_counts reads and clears them */
+    uint32_t early_ws, defer_ws;
+    uint32_t pad[28];
 };
 /* k_resident's grid barrier: one arrival counter per shard (blockIdx % 8, i.e. per XCD under
  * the round-robin placement), each on its own 128-byte line; kept in the parity region so it is
@@ -275,7 +287,9 @@ constexpr int RES_MAX_WG = 256;                     /* workgroups a resident lau
  * its workgroups; their workgroups issue their chunk's loads only once their window is known, so
  * the early group's chunks come off HBM first and its select overlaps the late group's stream
  * (round 5, with selector workgroups, cfg2: 0 / 25 / 45 / 60 / 80 / 99 % -> 28.1 / 27.8 / 26.1 /
- * 25.85 / 27.6 / 27.8 us, A/B on one box; 60 % puts one of the three 48-workgroup layers late) */
+ * 25.85 / 27.6 / 27.8 us, A/B on one box; 60 % puts one of the three 48-workgroup layers late;
+ * re-swept with the early stores, which share HBM with the late group's reads: 45 / 60 / 75 % ->
+ * 25.56 / 25.80 / 25.77 us, means of four alternated runs each, inside the 0.7 us spread: 60 kept) */
 constexpr int RES_LATE_PCT = 60;
 constexpr int RES_STG = 32;                         /* inside keys a thread may stage (of its 96; ~11 expected) */
 /* After the first segment barrier every workgroup publishes the keys of the (one or two)
@@ -307,6 +321,17 @@ constexpr uint32_t RES_POISON = 0x80000000u; /* a segment barrier counter whose 
 constexpr uint32_t RES_GR_OK = 1u;     /* the low word is the float32 threshold */
 constexpr uint32_t RES_GR_ALL = 2u;    /* the window missed: every float4 is rewritten */
 constexpr uint32_t RES_GR_FAULT = 4u;  /* a wait timed out: nobody stores */
+/* the bound granule's high word carries this bit (keys are < 2^31), so a published one is never 0 */
+constexpr uint32_t RES_BND_VALID = 0x80000000u;
+/* early stores of the resident launch (wtp_set_resident_early): 0 off, 1 on, 2 on and counted */
+/* the polling wave's own decided stores: true = with the other waves' (its poll of the threshold
+ * granule then waits behind them), false = only after the threshold granule, all 24 float4.  A/B
+ * on one box, cfg2, three alternated pairs against the form without early stores (26.7 - 27.0 us):
+ * false 26.7 - 26.8 us (no gain: an eighth of the chunk still leaves after the threshold), true
+ * 25.4 - 25.6 us (tools/resvar/early_polllate.sed builds the false form) */
+constexpr bool RES_EARLY_POLL_STORES = true;
+int set_resident_early(int mode); /* returns the previous mode */
+int resident_early();
 void launch_resident(const SegTable& t, SelHeader* head, uint32_t* cand, wtp_result* res, float* thr_out,
                      hipStream_t s);
 /* ---- the small-population path in one launch (small.hip, k_small) ----

@@ -231,6 +231,35 @@ def set_resident(enabled):
     return bool(N.lib().wtp_set_resident(1 if enabled else 0))
 
 
+def set_resident_early(mode):
+    """Early stores of the resident launch (include/wtprune.h wtp_set_resident_early): True / 1 on
+    (the default), False / 0 off, 2 on with the stores counted (resident_early_counts).  Identical
+    results in every mode.  Returns the previous mode."""
+    mode = (1 if mode else 0) if isinstance(mode, bool) else int(mode)
+    prev = int(N.lib().wtp_set_resident_early(mode))
+    if prev < 0:
+        raise ValueError(N.last_error())
+    return prev
+
+
+def resident_early_counts(device="cuda", stream=None):
+    """(early, deferred): the wave-wide float4 stores that resident launches on (device, stream)'s
+    workspace issued on the bound / held back for the threshold since the last read, counted in
+    mode 2 only; waits for the stream and clears the counters."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device(device.type, torch.cuda.current_device())
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    ws = workspace(device, 256, stream)
+    a, b = ctypes.c_ulonglong(0), ctypes.c_ulonglong(0)
+    rc = N.lib().wtp_resident_early_counts(ws.data_ptr(), ctypes.c_void_p(stream.cuda_stream), ctypes.byref(a),
+                                           ctypes.byref(b))
+    if rc != N.WTP_OK:
+        raise RuntimeError("libwtprune: %s (status %d)" % (N.last_error(), rc))
+    return int(a.value), int(b.value)
+
+
 def set_pipeline(enabled):
     """Overlap each launch group's selection with the next group's forward transform on a side
     stream (True / 1, the default); False / 0 one stream (include/wtprune.h wtp_set_pipeline).
