@@ -1,4 +1,4 @@
-"""Fused selection (include/wtprune.h wtp_set_fused_select; csrc/kernels.hip k_fwin /
+"""Fused selection (include/wtprune.h wtp_set_fused_select; csrc/select.inc k_fwin /
 k_fslot_collect, csrc/filterbank.hip k_fwd_int's classification): launch groups of large
 wavelet-transformed tensors take their percentile window from a transform of input patches
 before the forward, the forward classifies the coefficients as it writes them, and the packed
@@ -87,7 +87,7 @@ def test_fused_in_place(eng):
 
 
 def _patch_origins(R, C):
-    """k_fwin's patch origins (csrc/kernels.hip): rows at 1/8, 3/8, 5/8, 7/8 and columns at 3/8,
+    """k_fwin's patch origins (csrc/select.inc): rows at 1/8, 3/8, 5/8, 7/8 and columns at 3/8,
     7/8, 1/8, 5/8 of the free range, FWIN_PS = 128"""
     return [((R - 128) * lr // 8, (C - 128) * lc // 8) for lr, lc in zip((1, 3, 5, 7), (3, 7, 1, 5))]
 

@@ -9,7 +9,7 @@ T=$(mktemp -d)
 mkdir -p $T/w/csrc $T/include $R/tools/ab
 for f in $(git -C $R ls-tree --name-only $REV wavelettransforms_amd/csrc/); do git -C $R show $REV:$f > $T/w/csrc/$(basename $f); done
 for f in $(git -C $R ls-tree --name-only $REV include/); do git -C $R show $REV:$f > $T/include/$(basename $f); done
-cd $T/w/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -I. -I../../include \
-  -o $R/tools/ab/libwtprune_base.so *.hip  # every translation unit of that revision (abs.hip since the absolute-threshold method)
+# every translation unit of that revision (its *.hip files), with the working tree's build line
+python3 $R/wavelettransforms_amd/build.py --csrc $T/w/csrc --out $R/tools/ab/libwtprune_base.so
 rm -rf $T
 echo "built tools/ab/libwtprune_base.so from $REV"

@@ -13,6 +13,5 @@ while [ $# -gt 0 ]; do
   sed -i "$E" $T/w/csrc/$F
   if cmp -s $T/w/csrc/$F $T/w/csrc/$F.orig; then echo "variant $N: '$E' changed nothing in $F" >&2; exit 1; fi
 done
-cd $T/w/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -I. -I../../include \
-  -o $R/tools/ab/libwtprune_$N.so kernels.hip filterbank.hip small.hip api.hip
+python3 $R/wavelettransforms_amd/build.py --csrc $T/w/csrc --out $R/tools/ab/libwtprune_$N.so
 rm -rf $T

@@ -11,8 +11,7 @@ build_one() {
     cp $T/w/csrc/$f $T/o; sed -i "$e" $T/w/csrc/$f
     if cmp -s $T/o $T/w/csrc/$f; then echo "variant $v: '$e' changed nothing in $f" >&2; exit 1; fi
   done < $R/tools/resvar/$v.sed
-  (cd $T/w/csrc && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -ffp-contract=off -I. -I../../include \
-    -o $R/tools/ab/libwtprune_$v.so *.hip)
+  python3 $R/wavelettransforms_amd/build.py --csrc $T/w/csrc --out $R/tools/ab/libwtprune_$v.so
   rm -rf $T
   echo "built tools/ab/libwtprune_$v.so"
 }

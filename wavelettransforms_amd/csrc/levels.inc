@@ -1,0 +1,239 @@
+/*
+ * levels.inc -- the per-level filter-bank kernels and the small stream kernels beside them
+ * (k_copy_threshold, k_synth, k_count_small).
+ * Filter bank (pywt.wavedec2 / waverec2 periodization, :67-77): separable one-level passes
+ * whose every output is summed in PyWavelets' exact order (csrc/wt_dwt_core.h); the
+ * inverse thresholds coefficients as it loads them and the last pass crops and counts.
+ * Built with -ffp-contract=off: the float32 operation order IS the parity contract.
+ */
+#include "wtp_device.h"
+#include "wt_synth.h"
+
+#pragma clang fp contract(off)
+
+namespace wtp {
+
+/* ------------------------------------------------------------ filter bank --- */
+constexpr int DWT_THREADS = 256;
+
+__device__ __forceinline__ float thr_load(float c, float thr) { return (fabsf(c) < thr) ? 0.0f : c; }
+
+/* axis -2 analysis: in (B,R,C) -> L,H (B,Ro,C);  pywt dwtn first axis (_multidim.py:183-191) */
+__global__ __launch_bounds__(DWT_THREADS) void k_dwt_cols(const float* __restrict__ in, int64_t B, int64_t R,
+                                                          int64_t C, Taps tp, float* __restrict__ L,
+                                                          float* __restrict__ H) {
+    const int64_t Ro = (R + 1) / 2, total = B * Ro * C;
+    for (int64_t idx = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * DWT_THREADS) {
+        const int64_t c = idx % C, t = idx / C, o = t % Ro, b = t / Ro;
+        const float* x = in + b * R * C + c;
+        float a, d;
+        wt_ana_point(o, R, tp.F, tp.f[0], tp.f[1], [&](int64_t k) { return x[k * C]; }, a, d);
+        L[idx] = a;
+        H[idx] = d;
+    }
+}
+
+/* axis -1 analysis of L and H -> aa (next level / packed cA), ad, da, dd into the packed array */
+__global__ __launch_bounds__(DWT_THREADS) void k_dwt_rows(const float* __restrict__ L, const float* __restrict__ H,
+                                                          int64_t B, int64_t Ro, int64_t C, Taps tp,
+                                                          float* __restrict__ anext, float* __restrict__ P,
+                                                          int64_t PR, int64_t PC, int64_t offR, int64_t offC,
+                                                          int last) {
+    const int64_t Co = (C + 1) / 2, total = B * Ro * Co;
+    for (int64_t idx = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * DWT_THREADS) {
+        const int64_t o = idx % Co, t = idx / Co, r = t % Ro, b = t / Ro;
+        const float* lrow = L + (b * Ro + r) * C;
+        const float* hrow = H + (b * Ro + r) * C;
+        float aa, ad, da, dd;
+        wt_ana_point(o, C, tp.F, tp.f[0], tp.f[1], [&](int64_t k) { return lrow[k]; }, aa, ad);
+        wt_ana_point(o, C, tp.F, tp.f[0], tp.f[1], [&](int64_t k) { return hrow[k]; }, da, dd);
+        float* Pb = P + b * PR * PC;
+        if (last) Pb[r * PC + o] = aa;
+        else anext[idx] = aa;
+        Pb[r * PC + offC + o] = ad;
+        Pb[(offR + r) * PC + o] = da;
+        Pb[(offR + r) * PC + offC + o] = dd;
+    }
+}
+
+/* axis -1 synthesis: (aa,ad)->lo, (da,dd)->hi, each (B,R,2C); pywt idwtn (_multidim.py:288-309).
+ * Every coefficient read from the packed array is thresholded on load (np.where of :31). */
+__global__ __launch_bounds__(DWT_THREADS) void k_idwt_rows(const float* __restrict__ a, int64_t a_bs, int64_t lda,
+                                                           int a_from_P, const float* __restrict__ P, int64_t PR,
+                                                           int64_t PC, int64_t offR, int64_t offC, int64_t B,
+                                                           int64_t R, int64_t C, Taps tp, const float* thrp,
+                                                           float* __restrict__ lo, float* __restrict__ hi) {
+    const float thr = thrp ? *thrp : 0.0f; /* |c| < 0 never holds: no threshold */
+    const int64_t C2 = 2 * C, total = B * R * C2;
+    for (int64_t idx = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * DWT_THREADS) {
+        const int64_t n = idx % C2, t = idx / C2, r = t % R, b = t / R;
+        const float* Pb = P + b * PR * PC;
+        const float* arow = a_from_P ? Pb + r * PC : a + b * a_bs + r * lda;
+        const float* adr = Pb + r * PC + offC;
+        const float* dar = Pb + (offR + r) * PC;
+        const float* ddr = Pb + (offR + r) * PC + offC;
+        const float* rlo = tp.f[2];
+        const float* rhi = tp.f[3];
+        float vlo, vhi;
+        if (a_from_P)
+            vlo = wt_syn_point(n, C, tp.F, rlo, rhi, [&](int64_t k) { return thr_load(arow[k], thr); },
+                               [&](int64_t k) { return thr_load(adr[k], thr); });
+        else
+            vlo = wt_syn_point(n, C, tp.F, rlo, rhi, [&](int64_t k) { return arow[k]; },
+                               [&](int64_t k) { return thr_load(adr[k], thr); });
+        vhi = wt_syn_point(n, C, tp.F, rlo, rhi, [&](int64_t k) { return thr_load(dar[k], thr); },
+                           [&](int64_t k) { return thr_load(ddr[k], thr); });
+        lo[idx] = vlo;
+        hi[idx] = vhi;
+    }
+}
+
+/* axis -2 synthesis: lo,hi (B,R,C2) -> y (B,outH,outW) with outH <= 2R, outW <= C2 (crop);
+ * optionally counts exact zeros of y (the final level writes the pruned weights). */
+__global__ __launch_bounds__(DWT_THREADS) void k_idwt_cols(const float* __restrict__ lo, const float* __restrict__ hi,
+                                                           int64_t B, int64_t R, int64_t C2, Taps tp,
+                                                           float* __restrict__ y, int64_t outH, int64_t outW,
+                                                           unsigned long long* zero_count) {
+    const int64_t total = B * outH * outW;
+    unsigned long long z = 0;
+    for (int64_t idx = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; idx < total;
+         idx += (int64_t)gridDim.x * DWT_THREADS) {
+        const int64_t n = idx % outW, t = idx / outW, m = t % outH, b = t / outH;
+        const float* lc = lo + b * R * C2 + n;
+        const float* hc = hi + b * R * C2 + n;
+        const float v = wt_syn_point(m, R, tp.F, tp.f[2], tp.f[3], [&](int64_t k) { return lc[k * C2]; },
+                                     [&](int64_t k) { return hc[k * C2]; });
+        y[idx] = v;
+        z += (v == 0.0f);
+    }
+    if (zero_count) {
+        const unsigned long long tot = block_sum_u64<DWT_THREADS>(z);
+        if (threadIdx.x == 0 && tot) atomicAdd(zero_count, tot);
+    }
+}
+
+/* ---- 1-D flattened mode: pywt.wavedec / waverec (periodization) of the flattened tensor ----
+ * k_dwt1_level: one analysis level of a line of N samples -> a (ceil(N/2)) and d (ceil(N/2)),
+ * one thread per output pair, summed in PyWavelets' order (wt_ana_point). */
+__global__ __launch_bounds__(DWT_THREADS) void k_dwt1_level(const float* __restrict__ x, int64_t N, Taps tp,
+                                                            float* __restrict__ a, float* __restrict__ d) {
+    const int64_t M = (N + 1) / 2;
+    for (int64_t o = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; o < M; o += (int64_t)gridDim.x * DWT_THREADS) {
+        float sa, sd;
+        wt_ana_point(o, N, tp.F, tp.f[0], tp.f[1], [&](int64_t k) { return x[k]; }, sa, sd);
+        a[o] = sa;
+        d[o] = sd;
+    }
+}
+
+/* One synthesis level (pywt.waverec's loop body): a cropped to len(d) = N when it is one longer,
+ * idwt(a, d) -> 2N outputs, of which the first outN are written.  a_thr: threshold a on load
+ * (the packed cA of the top level); d is always a packed detail band (thresholded on load).
+ * thr == nullptr: no threshold.  The last level crops to the tensor and counts its zeros. */
+__global__ __launch_bounds__(DWT_THREADS) void k_idwt1_level(const float* __restrict__ a, int a_thr,
+                                                             const float* __restrict__ d, int64_t N, Taps tp,
+                                                             const float* __restrict__ thr, float* __restrict__ y,
+                                                             int64_t outN, unsigned long long* zero_count) {
+    const float t = thr ? *thr : 0.0f;
+    const bool ta = thr && a_thr, td = thr != nullptr;
+    unsigned long long z = 0;
+    for (int64_t n = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; n < outN; n += (int64_t)gridDim.x * DWT_THREADS) {
+        const float v = wt_syn_point(n, N, tp.F, tp.f[2], tp.f[3],
+                                     [&](int64_t k) { return ta ? thr_load(a[k], t) : a[k]; },
+                                     [&](int64_t k) { return td ? thr_load(d[k], t) : d[k]; });
+        y[n] = v;
+        z += (v == 0.0f);
+    }
+    if (zero_count) {
+        const unsigned long long tot = block_sum_u64<DWT_THREADS>(z);
+        if (threadIdx.x == 0 && tot) atomicAdd(zero_count, tot);
+    }
+}
+
+__global__ __launch_bounds__(DWT_THREADS) void k_copy_threshold(const float* __restrict__ P, float* __restrict__ out,
+                                                                int64_t n, const float* thrp,
+                                                                unsigned long long* zero_count) {
+    const float thr = thrp ? *thrp : 0.0f;
+    unsigned long long z = 0;
+    for (int64_t i = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * DWT_THREADS) {
+        const float v = thr_load(P[i], thr);
+        out[i] = v;
+        z += (v == 0.0f);
+    }
+    if (zero_count) {
+        const unsigned long long tot = block_sum_u64<DWT_THREADS>(z);
+        if (threadIdx.x == 0 && tot) atomicAdd(zero_count, tot);
+    }
+}
+
+__global__ __launch_bounds__(DWT_THREADS) void k_synth(float* __restrict__ out, int64_t n, uint64_t seed, uint32_t tid,
+                                                       int e) {
+    for (int64_t i = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * DWT_THREADS)
+        out[i] = wt_synth_value(seed, tid, (uint64_t)i, e);
+}
+
+/* calculate_sparsity (testing_suite/eval_model.py:7-20): #(|x| < thr) of one tensor */
+__global__ __launch_bounds__(STREAM_THREADS) void k_count_small(const float* __restrict__ x, int64_t n, float thr,
+                                                                unsigned long long* __restrict__ count) {
+    uint32_t c = 0;
+    for (int64_t i = (int64_t)blockIdx.x * STREAM_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * STREAM_THREADS)
+        c += fabsf(x[i]) < thr;
+    const unsigned long long tot = block_sum_u64<STREAM_THREADS>(c);
+    if (threadIdx.x == 0 && tot) atomicAdd(count, tot);
+}
+
+/* ---------------------------------------------------------------- launchers --- */
+static inline unsigned grid_for(int64_t total) {
+    int64_t g = (total + DWT_THREADS - 1) / DWT_THREADS;
+    if (g > 65536) g = 65536;
+    if (g < 1) g = 1;
+    return (unsigned)g;
+}
+
+void launch_dwt_cols(const float* in, int64_t B, int64_t R, int64_t C, const Taps& tp, float* L, float* H,
+                     hipStream_t s) {
+    hipLaunchKernelGGL(k_dwt_cols, dim3(grid_for(B * ((R + 1) / 2) * C)), dim3(DWT_THREADS), 0, s, in, B, R, C, tp,
+                       L, H);
+}
+void launch_dwt_rows(const float* L, const float* H, int64_t B, int64_t Ro, int64_t C, const Taps& tp, float* anext,
+                     float* P, int64_t PR, int64_t PC, int64_t offR, int64_t offC, int last, hipStream_t s) {
+    hipLaunchKernelGGL(k_dwt_rows, dim3(grid_for(B * Ro * ((C + 1) / 2))), dim3(DWT_THREADS), 0, s, L, H, B, Ro, C,
+                       tp, anext, P, PR, PC, offR, offC, last);
+}
+void launch_idwt_rows(const float* a, int64_t a_bs, int64_t lda, int a_from_P, const float* P, int64_t PR, int64_t PC,
+                      int64_t offR, int64_t offC, int64_t B, int64_t R, int64_t C, const Taps& tp, const float* thr,
+                      float* lo, float* hi, hipStream_t s) {
+    hipLaunchKernelGGL(k_idwt_rows, dim3(grid_for(B * R * 2 * C)), dim3(DWT_THREADS), 0, s, a, a_bs, lda, a_from_P,
+                       P, PR, PC, offR, offC, B, R, C, tp, thr, lo, hi);
+}
+void launch_idwt_cols(const float* lo, const float* hi, int64_t B, int64_t R, int64_t C, const Taps& tp, float* y,
+                      int64_t outH, int64_t outW, unsigned long long* zero_count, hipStream_t s) {
+    hipLaunchKernelGGL(k_idwt_cols, dim3(grid_for(B * outH * outW)), dim3(DWT_THREADS), 0, s, lo, hi, B, R, 2 * C, tp,
+                       y, outH, outW, zero_count);
+}
+void launch_dwt1_level(const float* x, int64_t N, const Taps& tp, float* a, float* d, hipStream_t s) {
+    hipLaunchKernelGGL(k_dwt1_level, dim3(grid_for((N + 1) / 2)), dim3(DWT_THREADS), 0, s, x, N, tp, a, d);
+}
+void launch_idwt1_level(const float* a, int a_thr, const float* d, int64_t N, const Taps& tp, const float* thr,
+                        float* y, int64_t outN, unsigned long long* zc, hipStream_t s) {
+    hipLaunchKernelGGL(k_idwt1_level, dim3(grid_for(outN)), dim3(DWT_THREADS), 0, s, a, a_thr, d, N, tp, thr, y, outN,
+                       zc);
+}
+void launch_copy_threshold(const float* P, float* out, int64_t n, const float* thr, unsigned long long* zc,
+                           hipStream_t s) {
+    hipLaunchKernelGGL(k_copy_threshold, dim3(grid_for(n)), dim3(DWT_THREADS), 0, s, P, out, n, thr, zc);
+}
+void launch_count_small(const float* x, int64_t n, float thr, unsigned long long* count, hipStream_t s) {
+    int64_t g = (n + STREAM_THREADS * 16 - 1) / (STREAM_THREADS * 16);
+    if (g > 4096) g = 4096;
+    if (g < 1) g = 1;
+    hipLaunchKernelGGL(k_count_small, dim3((unsigned)g), dim3(STREAM_THREADS), 0, s, x, n, thr, count);
+}
+void launch_synth(float* out, int64_t n, uint64_t seed, uint32_t tid, int e, hipStream_t s) {
+    hipLaunchKernelGGL(k_synth, dim3(grid_for(n)), dim3(DWT_THREADS), 0, s, out, n, seed, tid, e);
+}
+
+}  // namespace wtp

@@ -20,7 +20,7 @@
  * Every output sample is summed in PyWavelets' exact order: the tap tables built per level list
  * each output's (tap, source) pairs in wt_dwt_core.h's order, so results are bit-identical to
  * the per-level kernels and the oracle.  A barrier whose wait times out poisons the segment's
- * counter (res_wait in kernels.hip semantics): the whole segment stores nothing to `out` and
+ * counter (res_wait in resident.inc semantics): the whole segment stores nothing to `out` and
  * records WTP_PATH_FAULT, and the caller re-runs it in the multi-launch form.
  */
 #include "wtp_internal.h"
@@ -128,7 +128,7 @@ __device__ __forceinline__ int sm_wrap(int a, int N) { return a < N ? a : a - N;
 __device__ __forceinline__ int sm_r4(int x) { return (x + 3) & ~3; } /* LDS regions start 16-byte aligned */
 
 /* Cross-lane scan on DPP (row_shr inside rows of 16 lanes, row_bcast:15/31 across rows), as in
- * kernels.hip: a few VALU cycles per step where a shuffle pays an LDS round trip.  Whole wave. */
+ * wtp_device.h: a few VALU cycles per step where a shuffle pays an LDS round trip.  Whole wave. */
 template <int CTRL, int ROWM = 0xf, int BANKM = 0xf>
 __device__ __forceinline__ uint32_t sm_dpp(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWM, BANKM, false);

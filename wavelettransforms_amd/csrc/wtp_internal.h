@@ -254,7 +254,7 @@ struct Taps {
     float f[4][WTP_MAX_F]; /* dec_lo, dec_hi, rec_lo, rec_hi */
 };
 
-/* ---- launchers (kernels.hip) ---- */
+/* ---- launchers (select.inc, resident.inc, levels.inc, randprune.inc) ---- */
 void launch_window(const SegTable& t, SelHeader* head, hipStream_t s, const wtp_result* res = nullptr);
 /* the fused selection's retry of the segments whose select read MODE_RETRY (t.retry = 1, chunk
  * units): k_window, a grid-stride k_collect over their chunks, k_mask_select -- a few us when
