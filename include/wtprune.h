@@ -16,6 +16,7 @@
  *   wtp_threshold_f32               percentile_based_thresholding     dwt_pruning.py:25-32
  *   wtp_wavedec2_f32                pywt.wavedec2 + coeffs_to_array   dwt_pruning.py:67-70
  *   wtp_waverec2_f32                array_to_coeffs + waverec2 + crop dwt_pruning.py:75-82
+ *   wtp_prune_mode_f32              multi_resolution_analysis(mode=)  dwt_pruning.py:35, :67-68, :77
  *   wtp_prune_abs_f32               multi_resolution_analysis         dwt_pruning_NoEntropy.py:29-60
  *   wtp_synth_f32                   (test/bench input generator, no reference counterpart)
  */
@@ -119,6 +120,56 @@ int wtp_prune_layers_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id
 size_t wtp_workspace_size_ex(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int flags);
 int wtp_prune_ex_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double pct, int flags,
                      void* workspace, size_t workspace_bytes, wtp_result* results_dev, wtp_stream_t stream);
+
+/* ---- PyWavelets' signal-extension modes: the `mode` argument of multi_resolution_analysis
+ * (dwt_pruning.py:35), handed to pywt.wavedec2 / waverec2 (:67-68, :77) ----
+ * wtp_prune_mode_f32 is wtp_prune_ex_f32 with a mode: WTP_MODE_PERIODIZATION is that entry
+ * itself; zero, constant, symmetric, reflect and periodic run the same path with the mode's
+ * geometry, bit for bit as PyWavelets 1.1.1 computes it in float32:
+ *   - a level turns a side N into floor((N + F - 1) / 2) coefficients (not ceil(N / 2)), so the
+ *     packed array of coeffs_to_array is larger than the tensor and in general not tight; its
+ *     padding zeros belong to the percentile's population (coeff_numel counts them);
+ *   - a level's synthesis gives 2N - F + 2 samples; waverec2 drops one between levels where that
+ *     is one more than the next level's detail bands hold;
+ *   - the result (2 R1 - F + 2, 2 C1 - F + 2) is H + (H odd) by W + (W odd): a 4-D tensor is
+ *     cropped by :79-82, a 2-D or 3-D tensor with an odd side is WTP_ECROP (an odd Linear weight
+ *     included), as under periodization.
+ * The level clamp (pywt.dwt_max_level) does not depend on the mode, and a tensor whose clamped
+ * level is 0, or with ndim < 2, takes exactly the periodization path (byte-identical results).
+ * smooth, antisymmetric and antireflect have ids but are not implemented (WTP_EARG), WTP_FLATTEN
+ * with any mode but periodization is WTP_EARG, and so is a wavelet of odd filter length under an
+ * extension mode.  Tensors whose images are at most 8 x 8 run their whole forward transform in
+ * one launch and their whole inverse transform in another, each image held on chip in between
+ * its read and its write; larger ones run a level at a time.  Same rules as every entry: stream-
+ * ordered, no allocation, no synchronisation, capturable, out may alias in, validation before any
+ * device work.  Workspace: wtp_workspace_size_mode bytes (0 if the request is invalid), shared with
+ * and initialised like wtp_prune_f32's. */
+#define WTP_MODE_PERIODIZATION 0
+#define WTP_MODE_ZERO 1
+#define WTP_MODE_CONSTANT 2
+#define WTP_MODE_SYMMETRIC 3
+#define WTP_MODE_REFLECT 4
+#define WTP_MODE_PERIODIC 5
+#define WTP_MODE_SMOOTH 6        /* known to pywt, not implemented here */
+#define WTP_MODE_ANTISYMMETRIC 7 /* " */
+#define WTP_MODE_ANTIREFLECT 8   /* " */
+int wtp_mode_id(const char* name);       /* -1 if pywt would reject the name */
+const char* wtp_mode_name(int mode_id);  /* NULL for an unknown id */
+/* pywt.coeffs_to_array's shape for an H x W image (the level is taken as given, not clamped) */
+int wtp_packed_shape_mode(int64_t H, int64_t W, int wavelet_id, int level, int mode_id, int64_t* rows, int64_t* cols);
+size_t wtp_workspace_size_mode(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int flags,
+                               int mode_id);
+int wtp_prune_mode_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double pct, int flags,
+                       int mode_id, void* workspace, size_t workspace_bytes, wtp_result* results_dev,
+                       wtp_stream_t stream);
+/* components, as wtp_wavedec2_f32 / wtp_waverec2_f32 below (level as given; packed: (B, rows,
+ * cols) of wtp_packed_shape_mode, padding zeroed; waverec2 crops to H x W) */
+size_t wtp_dwt_workspace_size_mode(int64_t B, int64_t H, int64_t W, int wavelet_id, int level, int mode_id);
+int wtp_wavedec2_mode_f32(const float* in, float* packed, int64_t B, int64_t H, int64_t W, int wavelet_id,
+                          int level, int mode_id, void* workspace, size_t workspace_bytes, wtp_stream_t stream);
+int wtp_waverec2_mode_f32(const float* packed, float* out, int64_t B, int64_t H, int64_t W, int wavelet_id,
+                          int level, int mode_id, const float* thr32_dev, void* workspace, size_t workspace_bytes,
+                          wtp_stream_t stream);
 
 /* ---- the absolute-threshold method: multi_resolution_analysis of
  * ResNet/dwt_pruning_NoEntropy.py:29-60 over a list of tensors ----

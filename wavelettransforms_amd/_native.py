@@ -76,6 +76,14 @@ def lib():
             "wtp_prune_layers_f32": ([tp, i32, i32, i32, f64, vp, sz, vp, vp], i32),
             "wtp_workspace_size_ex": ([tp, i32, i32, i32, i32], sz),
             "wtp_prune_ex_f32": ([tp, i32, i32, i32, f64, i32, vp, sz, vp, vp], i32),
+            "wtp_mode_id": ([ctypes.c_char_p], i32),
+            "wtp_mode_name": ([i32], ctypes.c_char_p),
+            "wtp_packed_shape_mode": ([i64, i64, i32, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
+            "wtp_workspace_size_mode": ([tp, i32, i32, i32, i32, i32], sz),
+            "wtp_prune_mode_f32": ([tp, i32, i32, i32, f64, i32, i32, vp, sz, vp, vp], i32),
+            "wtp_dwt_workspace_size_mode": ([i64, i64, i64, i32, i32, i32], sz),
+            "wtp_wavedec2_mode_f32": ([vp, vp, i64, i64, i64, i32, i32, i32, vp, sz, vp], i32),
+            "wtp_waverec2_mode_f32": ([vp, vp, i64, i64, i64, i32, i32, i32, vp, vp, sz, vp], i32),
             "wtp_abs_workspace_size": ([tp, i32, i32, i32], sz),
             "wtp_prune_abs_f32": ([tp, i32, i32, i32, f64, vp, sz, vp, vp], i32),
             "wtp_threshold_f32": ([vp, vp, i64, f64, vp, sz, vp, vp], i32),

@@ -18,9 +18,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(OUT_DIR, "libwtprune.so")
-SOURCES = ["prune_unit.hip", "filterbank.hip", "small.hip", "abs.hip", "api.hip"]
+SOURCES = ["prune_unit.hip", "filterbank.hip", "small.hip", "abs.hip", "modes.hip", "api.hip"]
 DEPS = SOURCES + ["select.inc", "resident.inc", "levels.inc", "randprune.inc", "wtp_internal.h", "wtp_device.h",
-                  "wtp_select.h", "wt_dwt_core.h", "wt_abs_core.h", "wt_synth.h",
+                  "wtp_select.h", "wt_dwt_core.h", "wt_abs_core.h", "wt_modes_core.h", "wt_synth.h",
                   "wt_perm.h", "wt_filters.inc", "small_geom.h", "fb_index.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("WTP_OFFLOAD_ARCH", "gfx950")

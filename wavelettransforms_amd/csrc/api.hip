@@ -92,6 +92,8 @@ struct TPlan {
     size_t f_off = 0;     /* workspace byte offset of its slot area (per group parity and slot) */
     int64_t len[34] = {}; /* flat: len[0] = numel, len[k] = ceil(len[k-1] / 2)              */
     bool strict = false;  /* unclamped levels (wtp_prune_abs_f32): lvl_tiled keeps short sides per-point */
+    int mode = 0;         /* WTP_MODE_* of a transform that runs in modes.hip (0: the periodized kernels) */
+    int tiny_lg = -1;     /* mode != 0: log2 of the lanes k_mtiny_* give the tensor's images (-1: per-level kernels) */
 };
 
 struct Layout {
@@ -136,7 +138,7 @@ int64_t cap_for(int64_t n, bool dwt) {
 
 /* Validate and plan every tensor in the reference's order; returns WTP_OK or the first error. */
 int plan_tensors(const wtp_tensor* ts, int n, int wid, int level, double pct, bool check_ptrs,
-                 std::vector<TPlan>& out, bool carry = true, bool flat = false) {
+                 std::vector<TPlan>& out, bool carry = true, bool flat = false, int mode = WTP_MODE_PERIODIZATION) {
     out.assign(n, TPlan());
     int cur_level = level;
     for (int t = 0; t < n; ++t) {
@@ -187,19 +189,25 @@ int plan_tensors(const wtp_tensor* ts, int n, int wid, int level, double pct, bo
             p.L = cur_level;
             if (p.L < 0) return fail(WTP_EBADLEVEL, t, "Level value of %d is too low . Minimum level is 0.", p.L);
             if (p.L > 32) return fail(WTP_EARG, t, "tensor %d: level %d unsupported", t, p.L);
-            wt_geom(p.H, p.W, p.L, &p.g);
+            /* level 0 is the same in every mode: it keeps the periodized plan (and its kernels) */
+            p.dwt = p.L > 0;
+            p.mode = p.dwt ? mode : WTP_MODE_PERIODIZATION;
+            const int F = wt_flen[wid];
+            if (p.mode && !wtm_levels_ok(p.H, p.W, p.L, F, p.mode))
+                return fail(WTP_EARG, t, "tensor %d: the mode cannot extend its lines (an odd filter length, or reflect "
+                            "of a one-sample line)", t);
+            wtm_geom(p.H, p.W, p.L, F, p.mode, &p.g);
             p.pop = p.B * p.g.PR * p.g.PC;
             if (!pct_ok(pct)) return fail(WTP_EBADPCT, t, "Percentiles must be in the range [0, 100]");
             if (p.pop == 0) return fail(WTP_EEMPTY, t, "index -1 is out of bounds for axis 0 with size 0");
-            p.dwt = p.L > 0;
             if (p.dwt) {
-                int64_t nc = p.g.R[p.L] * p.g.C[p.L];
-                for (int k = 1; k <= p.L; ++k) nc += 3 * p.g.R[k] * p.g.C[k];
-                p.tight = nc == p.g.PR * p.g.PC;
-                /* waverec2 yields (2R1, 2C1); the 4-index crop of :79-82 then fails for 2-D/3-D
+                p.tight = wtm_block_cells(&p.g, p.L) == p.g.PR * p.g.PC;
+                if (p.mode && p.B <= (int64_t)INT32_MAX) p.tiny_lg = wtm_tiny_lanes_log2(p.H, p.W, p.L, F);
+                /* waverec2 yields (2R1, 2C1), under an extension mode (2R1 - F + 2, 2C1 - F + 2);
+                 * the 4-index crop of :79-82 then fails for 2-D/3-D
                  * tensors (IndexError), cannot crop W for 5-D or anything for >= 6-D (the
                  * later .view(original_shape) raises RuntimeError) */
-                const bool hbad = 2 * p.g.R[1] != p.H, wbad = 2 * p.g.C[1] != p.W;
+                const bool hbad = wtm_out_len(p.g.R[1], F, p.mode) != p.H, wbad = wtm_out_len(p.g.C[1], F, p.mode) != p.W;
                 if ((x.ndim < 4 && (hbad || wbad)) || (x.ndim == 5 && wbad) || (x.ndim >= 6 && (hbad || wbad)))
                     return fail(WTP_ECROP, t, x.ndim < 4 ? "tuple index out of range"
                                                          : "shape is invalid for input of this size");
@@ -230,6 +238,11 @@ bool lvl_tiled(const TPlan& p, int64_t B, int64_t R, int64_t C, const Taps& tp) 
 size_t temp_elems(const TPlan& p, const Taps& tp) {
     if (p.flat) return (size_t)p.numel + 2; /* two ping-pong lines of up to numel + 1 samples */
     int64_t need = 0;
+    if (p.mode) { /* modes.hip: a half transform of either direction (R[k] x C[k-1]), an approximation */
+        if (p.tiny_lg >= 0) return 0;
+        for (int k = 1; k <= p.L; ++k) need = std::max(need, p.B * p.g.R[k] * std::max(p.g.C[k - 1], p.g.C[k]));
+        return (size_t)need;
+    }
     for (int k = 1; k <= p.L; ++k) {
         const int64_t R0 = p.g.R[k - 1], C0 = p.g.C[k - 1], R = p.g.R[k], C = p.g.C[k];
         need = std::max(need, p.B * R * (lvl_tiled(p, p.B, R0, C0, tp) ? C : C0));
@@ -248,7 +261,7 @@ size_t temp_elems(const TPlan& p, const Taps& tp) {
  * not known yet, so the slots are reserved whenever the shape qualifies. */
 constexpr int64_t FUSED_MIN_POP = (int64_t)1 << 22;
 int64_t fused_slot_count(const TPlan& p, const float* in, const Taps& tp, bool sizing) {
-    if (!p.dwt || p.flat || !p.tight || p.L < 1 || p.L > 6 || p.pop < FUSED_MIN_POP) return 0;
+    if (!p.dwt || p.flat || p.mode || !p.tight || p.L < 1 || p.L > 6 || p.pop < FUSED_MIN_POP) return 0;
     if (p.g.R[0] < FWIN_PS || p.g.C[0] < FWIN_PS) return 0;
     int64_t tot = 0;
     for (int k = 1; k <= p.L; ++k) {
@@ -373,6 +386,38 @@ struct Chain {
     uint32_t* fsl = nullptr; /* fused selection: the tensor's slot area (null: not fused) */
 };
 
+/* The chains whose images are tiny under an extension mode (TPlan::tiny_lg): all of them in one
+ * launch of k_mtiny_fwd (every analysis level, the packed image with its padding zeros) or of
+ * k_mtiny_inv (threshold on load, every synthesis level, the crops, the zero count). */
+void launch_tiny_chains(const std::vector<Chain>& cs, const Taps& tp, hipStream_t s, bool inverse) {
+    MTinyTable tab;
+    memset(&tab, 0, sizeof tab);
+    for (const Chain& c : cs) {
+        const TPlan& p = *c.p;
+        if (p.tiny_lg < 0) continue;
+        MTinySeg& sg = tab.s[tab.nseg];
+        sg.in = c.in;
+        sg.out = c.out;
+        sg.P = c.P;
+        sg.thr = c.thr;
+        sg.zc = c.zc;
+        sg.B = (int32_t)p.B;
+        sg.H = (uint8_t)p.H;
+        sg.W = (uint8_t)p.W;
+        sg.L = (uint8_t)p.L;
+        sg.nl_log2 = (uint8_t)p.tiny_lg;
+        tab.mode = p.mode;
+        tab.wave_begin[tab.nseg++] = tab.nwave;
+        tab.nwave += (int32_t)((p.B + (1 << p.tiny_lg) - 1) >> p.tiny_lg);
+    }
+    if (!tab.nseg) return;
+    tab.F = tp.F;
+    for (int k = 0; k < 4; ++k)
+        for (int j = 0; j < tp.F && j < MT_F_MAX; ++j) tab.f[k][j] = tp.f[k][j];
+    if (inverse) launch_mtiny_inv(tab, s);
+    else launch_mtiny_fwd(tab, s);
+}
+
 /* pywt.wavedec2 (dwt_pruning.py:67-68) of every chain into its packed layout.  Level k of all
  * chains is ONE tiled launch (filterbank.hip) where the level is large enough, else the two
  * per-point passes of that chain.  Each approximation ping-pongs between the chain's own temps
@@ -385,13 +430,20 @@ void forward_chains(const std::vector<Chain>& cs, const Taps& tp, hipStream_t s,
     std::vector<uint32_t*> fcur(cs.size()); /* fused selection: each chain's next level's slots */
     for (size_t j = 0; j < cs.size(); ++j) fcur[j] = (fused && cs[j].fsl) ? cs[j].fsl + FSL_HDR_WORDS : nullptr;
     std::vector<FwdItem> items;
+    launch_tiny_chains(cs, tp, s, false);
     for (int k = 1; k <= maxL; ++k) {
         items.clear();
         for (size_t j = 0; j < cs.size(); ++j) {
             const TPlan& p = *cs[j].p;
-            if (p.L < k) continue;
+            if (p.L < k || p.tiny_lg >= 0) continue;
             float *tL = cs[j].T[0], *tH = cs[j].T[1], *tA = cs[j].T[2];
             const int64_t R0 = p.g.R[k - 1], C0 = p.g.C[k - 1];
+            if (p.mode) { /* both passes through tL / tH, the approximations in tA */
+                launch_mdwt_level(cur[j], p.B, R0, C0, p.g.R[k], p.g.C[k], tp, p.mode, tL, tH, tA, cs[j].P, p.g.PR,
+                                  p.g.PC, p.g.offR[k], p.g.offC[k], k == p.L, s);
+                cur[j] = tA;
+                continue;
+            }
             if (lvl_tiled(p, p.B, R0, C0, tp)) {
                 float* an = (cur[j] == tA) ? tL : tA;
                 items.push_back(FwdItem{cur[j], p.B, R0, C0, an, cs[j].P, p.g.PR, p.g.PC, p.g.offR[k], p.g.offC[k],
@@ -425,14 +477,22 @@ void inverse_chains(const std::vector<Chain>& cs, const Taps& tp, hipStream_t s)
     for (const Chain& c : cs) maxL = std::max(maxL, c.p->L);
     std::vector<const float*> cur(cs.size(), nullptr); /* nullptr: the packed cA */
     std::vector<InvItem> items;
+    launch_tiny_chains(cs, tp, s, true);
     for (int k = maxL; k >= 1; --k) {
         items.clear();
         for (size_t j = 0; j < cs.size(); ++j) {
             const TPlan& p = *cs[j].p;
-            if (p.L < k) continue;
+            if (p.L < k || p.tiny_lg >= 0) continue;
             float *tL = cs[j].T[0], *tH = cs[j].T[1], *tA = cs[j].T[2];
             const int64_t R = p.g.R[k], C = p.g.C[k];
             const bool fromP = k == p.L;
+            if (p.mode) { /* every level writes R[k-1] x C[k-1]: waverec2's crop between the levels, the
+                           * reference's crop after the last (wt_modes_core.h) */
+                launch_midwt_level(fromP ? nullptr : tA, fromP, cs[j].P, p.g.PR, p.g.PC, p.g.offR[k], p.g.offC[k], p.B,
+                                   R, C, tp, cs[j].thr, tL, tH, k == 1 ? cs[j].out : tA, p.g.R[k - 1], p.g.C[k - 1],
+                                   k == 1 ? cs[j].zc : nullptr, s);
+                continue;
+            }
             const int64_t a_bs = fromP ? 0 : 4 * p.g.R[k + 1] * p.g.C[k + 1];
             const int64_t lda = fromP ? 0 : 2 * p.g.C[k + 1];
             const bool final = k == 1;
@@ -513,7 +573,7 @@ bool plan_small(const std::vector<TPlan>& ps, const wtp_tensor* ts, int n, void*
     const int cap = std::min(small_capacity(), RES_MAX_WG);
     int64_t tot = 0;
     for (const TPlan& p : ps) {
-        if (!p.dwt || p.flat || p.L > SM_LMAX || p.H > SM_LINE_MAX || p.W > SM_LINE_MAX) return false;
+        if (!p.dwt || p.flat || p.mode || p.L > SM_LMAX || p.H > SM_LINE_MAX || p.W > SM_LINE_MAX) return false;
         tot += p.pop;
     }
     if (tot > SM_POP_MAX || cap < n) return false;
@@ -737,13 +797,13 @@ SidePipe* side_pipe(hipStream_t s, int nev) {
 
 static int prune_impl(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double pct, void* ws,
                       size_t ws_bytes, wtp_result* results, wtp_stream_t stream, bool carry, bool flat = false,
-                      bool no_resident = false) {
+                      bool no_resident = false, int mode = WTP_MODE_PERIODIZATION) {
     g_err.clear();
     g_err_tensor = -1;
     if (ntensors < 0 || (ntensors > 0 && (!tensors || !results))) return fail(WTP_EARG, -1, "bad arguments");
     if (ntensors == 0) return WTP_OK;
     std::vector<TPlan> ps;
-    int rc = plan_tensors(tensors, ntensors, wavelet_id, level, pct, true, ps, carry, flat);
+    int rc = plan_tensors(tensors, ntensors, wavelet_id, level, pct, true, ps, carry, flat, mode);
     if (rc != WTP_OK) return rc;
     const Taps tp = (wavelet_id >= 0 && wavelet_id < WT_NUM_WAVELETS) ? make_taps(wavelet_id) : Taps{};
     Layout lay = make_layout(ps, tp);
@@ -788,7 +848,10 @@ static int prune_impl(const wtp_tensor* tensors, int ntensors, int wavelet_id, i
         c.zc = reinterpret_cast<unsigned long long*>(&results[t].zero_count);
         if (p.f_slots) c.fsl = reinterpret_cast<uint32_t*>(wsb(ws, p.f_off));
         gchains[t / SEG_PER_LAUNCH].push_back(c);
-        if (!p.tight && hipMemsetAsync(c.P, 0, (size_t)p.pop * sizeof(float), s) != hipSuccess)
+        if (p.mode) { /* the padding zeros by a kernel (a memset node misbehaved in a replayed graph:
+                       * k_abs_init's note); k_mtiny_fwd writes whole packed images itself */
+            if (!p.tight && p.tiny_lg < 0) launch_abs_zero(c.P, p.pop, s);
+        } else if (!p.tight && hipMemsetAsync(c.P, 0, (size_t)p.pop * sizeof(float), s) != hipSuccess)
             return fail(WTP_EHIP, t, "hipMemsetAsync failed");
     }
     int dwt_groups = 0;
@@ -1055,6 +1118,63 @@ int wtp_prune_ex_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, in
     if (flags & ~(WTP_CARRY_LEVEL | WTP_FLATTEN | WTP_NO_RESIDENT)) return fail(WTP_EARG, -1, "bad flags 0x%x", flags);
     return prune_impl(tensors, ntensors, wavelet_id, level, pct, ws, ws_bytes, results, stream,
                       (flags & WTP_CARRY_LEVEL) != 0, (flags & WTP_FLATTEN) != 0, (flags & WTP_NO_RESIDENT) != 0);
+}
+
+/* ---- PyWavelets' signal-extension modes (dwt_pruning.py:35, the `mode` argument) ---- */
+static const char* const g_mode_names[] = {"periodization", "zero", "constant", "symmetric", "reflect", "periodic",
+                                           "smooth", "antisymmetric", "antireflect"};
+int wtp_mode_id(const char* name) {
+    if (!name) return -1;
+    for (int i = 0; i < (int)(sizeof g_mode_names / sizeof g_mode_names[0]); ++i)
+        if (strcmp(name, g_mode_names[i]) == 0) return i;
+    return -1;
+}
+const char* wtp_mode_name(int mode_id) {
+    return (mode_id >= 0 && mode_id < (int)(sizeof g_mode_names / sizeof g_mode_names[0])) ? g_mode_names[mode_id] : nullptr;
+}
+
+/* 0 when the mode and the flags can run; else the error is set */
+static int mode_check(int mode_id, int flags) {
+    if (flags & ~(WTP_CARRY_LEVEL | WTP_FLATTEN | WTP_NO_RESIDENT)) return fail(WTP_EARG, -1, "bad flags 0x%x", flags);
+    if (mode_id < 0 || mode_id > WTP_MODE_ANTIREFLECT) return fail(WTP_EARG, -1, "Unknown mode id %d", mode_id);
+    if (!wtm_mode_known(mode_id))
+        return fail(WTP_EARG, -1, "mode '%s' is not implemented", g_mode_names[mode_id]);
+    if (mode_id != WTP_MODE_PERIODIZATION && (flags & WTP_FLATTEN))
+        return fail(WTP_EARG, -1, "WTP_FLATTEN runs under periodization only");
+    return WTP_OK;
+}
+
+int wtp_packed_shape_mode(int64_t H, int64_t W, int wavelet_id, int level, int mode_id, int64_t* rows, int64_t* cols) {
+    if (level < 0 || level > 32 || !rows || !cols || H < 1 || W < 1) return fail(WTP_EARG, -1, "bad packed-shape request");
+    if (wavelet_id < 0 || wavelet_id >= WT_NUM_WAVELETS) return fail(WTP_EBADWAVELET, -1, "Unknown wavelet name");
+    int rc = mode_check(mode_id, 0);
+    if (rc != WTP_OK) return rc;
+    const int F = wt_flen[wavelet_id];
+    if (level > 0 && !wtm_levels_ok(H, W, level, F, mode_id)) return fail(WTP_EARG, -1, "bad packed-shape request");
+    wt_level_geom g;
+    wtm_geom(H, W, level, F, level > 0 ? mode_id : 0, &g);
+    *rows = g.PR;
+    *cols = g.PC;
+    return WTP_OK;
+}
+
+size_t wtp_workspace_size_mode(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int flags,
+                               int mode_id) {
+    if (ntensors < 0 || (ntensors > 0 && !tensors) || mode_check(mode_id, flags) != WTP_OK) return 0;
+    std::vector<TPlan> ps;
+    if (plan_tensors(tensors, ntensors, wavelet_id, level, 50.0, false, ps, (flags & WTP_CARRY_LEVEL) != 0,
+                     (flags & WTP_FLATTEN) != 0, mode_id) != WTP_OK)
+        return 0;
+    const Taps tp = (wavelet_id >= 0 && wavelet_id < WT_NUM_WAVELETS) ? make_taps(wavelet_id) : Taps{};
+    return make_layout(ps, tp).total;
+}
+
+int wtp_prune_mode_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double pct, int flags,
+                       int mode_id, void* ws, size_t ws_bytes, wtp_result* results, wtp_stream_t stream) {
+    int rc = mode_check(mode_id, flags);
+    if (rc != WTP_OK) return rc;
+    return prune_impl(tensors, ntensors, wavelet_id, level, pct, ws, ws_bytes, results, stream,
+                      (flags & WTP_CARRY_LEVEL) != 0, (flags & WTP_FLATTEN) != 0, (flags & WTP_NO_RESIDENT) != 0, mode_id);
 }
 
 /* ---------------------------------------------------------- min pruning --- */
@@ -1466,6 +1586,65 @@ int wtp_waverec2_f32(const float* packed, float* out, int64_t B, int64_t H, int6
     float* tH = reinterpret_cast<float*>(wsb(ws, one));
     float* tA = reinterpret_cast<float*>(wsb(ws, 2 * one));
     inverse_chains({Chain{&p, nullptr, out, const_cast<float*>(packed), {tL, tH, tA}, thr32, nullptr}}, make_taps(wid), s);
+    return check_launch();
+}
+
+/* components under an extension mode: the requested level as given (no clamp), the per-level
+ * kernels of modes.hip; periodization is the entries above */
+static int component_plan_mode(int64_t B, int64_t H, int64_t W, int wid, int level, int mode_id, TPlan& p) {
+    int rc = mode_check(mode_id, 0);
+    if (rc != WTP_OK) return rc;
+    rc = component_plan(B, H, W, wid, level, p);
+    if (rc != WTP_OK || mode_id == WTP_MODE_PERIODIZATION || level == 0) return rc;
+    const int F = wt_flen[wid];
+    if (!wtm_levels_ok(H, W, level, F, mode_id))
+        return fail(WTP_EARG, -1, "the mode cannot extend a %lld x %lld image under a %d-tap filter at level %d",
+                    (long long)H, (long long)W, F, level);
+    p.mode = mode_id;
+    wtm_geom(H, W, level, F, mode_id, &p.g);
+    p.pop = B * p.g.PR * p.g.PC;
+    p.tight = wtm_block_cells(&p.g, level) == p.g.PR * p.g.PC;
+    if (p.pop > (int64_t)INT32_MAX) return fail(WTP_EARG, -1, "more than 2^31-1 coefficients");
+    return WTP_OK;
+}
+
+size_t wtp_dwt_workspace_size_mode(int64_t B, int64_t H, int64_t W, int wavelet_id, int level, int mode_id) {
+    TPlan p;
+    if (component_plan_mode(B, H, W, wavelet_id, level, mode_id, p) != WTP_OK) return 0;
+    if (!p.mode) return wtp_dwt_workspace_size(B, H, W, level);
+    return 3 * align_up(temp_elems(p, Taps{}) * sizeof(float));
+}
+
+int wtp_wavedec2_mode_f32(const float* in, float* packed, int64_t B, int64_t H, int64_t W, int wid, int level,
+                          int mode_id, void* ws, size_t ws_bytes, wtp_stream_t stream) {
+    TPlan p;
+    int rc = component_plan_mode(B, H, W, wid, level, mode_id, p);
+    if (rc != WTP_OK) return rc;
+    if (!p.mode) return wtp_wavedec2_f32(in, packed, B, H, W, wid, level, ws, ws_bytes, stream);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t one = align_up(temp_elems(p, Taps{}) * sizeof(float));
+    if (!ws || ws_bytes < 3 * one) return fail(WTP_EWORKSPACE, -1, "workspace too small: need %zu", 3 * one);
+    if (!p.tight && hipMemsetAsync(packed, 0, (size_t)p.pop * sizeof(float), s) != hipSuccess)
+        return fail(WTP_EHIP, -1, "hipMemsetAsync failed");
+    float* T[3];
+    for (int i = 0; i < 3; ++i) T[i] = reinterpret_cast<float*>(wsb(ws, i * one));
+    forward_chains({Chain{&p, in, nullptr, packed, {T[0], T[1], T[2]}, nullptr, nullptr}}, make_taps(wid), s);
+    return check_launch();
+}
+
+int wtp_waverec2_mode_f32(const float* packed, float* out, int64_t B, int64_t H, int64_t W, int wid, int level,
+                          int mode_id, const float* thr32, void* ws, size_t ws_bytes, wtp_stream_t stream) {
+    TPlan p;
+    int rc = component_plan_mode(B, H, W, wid, level, mode_id, p);
+    if (rc != WTP_OK) return rc;
+    if (!p.mode) return wtp_waverec2_f32(packed, out, B, H, W, wid, level, thr32, ws, ws_bytes, stream);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t one = align_up(temp_elems(p, Taps{}) * sizeof(float));
+    if (!ws || ws_bytes < 3 * one) return fail(WTP_EWORKSPACE, -1, "workspace too small: need %zu", 3 * one);
+    float* T[3];
+    for (int i = 0; i < 3; ++i) T[i] = reinterpret_cast<float*>(wsb(ws, i * one));
+    inverse_chains({Chain{&p, nullptr, out, const_cast<float*>(packed), {T[0], T[1], T[2]}, thr32, nullptr}},
+                   make_taps(wid), s);
     return check_launch();
 }
 

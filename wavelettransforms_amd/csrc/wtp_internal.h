@@ -9,6 +9,7 @@
 #include "../../include/wtprune.h"
 #include "wt_dwt_core.h"
 #include "wt_abs_core.h"
+#include "wt_modes_core.h"
 
 #pragma clang fp contract(off)
 
@@ -485,6 +486,38 @@ void launch_abs_zero(float* p, int64_t n, hipStream_t s);
 void launch_abs_tiny(const AbsTable& t, wtp_abs_result* res, hipStream_t s);
 void launch_abs_count(const float* x, int64_t n, unsigned long long* dst, wtp_abs_result* rec,
                       const wtp_abs_result& init, hipStream_t s);
+/* ---- the extension modes (modes.hip; arithmetic and geometry: wt_modes_core.h) ----
+ * one level of one tensor, per-point: the two analysis passes through tL / tH, the two synthesis
+ * passes through tL / tH (the level's output cropped to oH x oW) */
+void launch_mdwt_level(const float* in, int64_t B, int64_t R, int64_t C, int64_t Ro, int64_t Co, const Taps& tp,
+                       int mode, float* tL, float* tH, float* anext, float* P, int64_t PR, int64_t PC, int64_t offR,
+                       int64_t offC, int last, hipStream_t s);
+void launch_midwt_level(const float* a, int a_from_P, const float* P, int64_t PR, int64_t PC, int64_t offR,
+                        int64_t offC, int64_t B, int64_t R, int64_t C, const Taps& tp, const float* thr, float* tL,
+                        float* tH, float* y, int64_t oH, int64_t oW, unsigned long long* zc, hipStream_t s);
+/* k_mtiny_fwd / k_mtiny_inv: one wave per workgroup and per NL images of one tensor (the lane
+ * choice wtm_tiny_lanes_log2), the tiny tensors of one launch group per launch */
+constexpr int MT_THREADS = 64;
+constexpr int MT_LMAX = WTM_TINY_LMAX;
+constexpr int MT_F_MAX = WTM_TINY_F_MAX;
+constexpr int MT_WAVE_WORDS = WTM_WAVE_WORDS;
+struct MTinySeg {
+    const float* in;
+    float* out;
+    float* P;                  /* packed coefficients (workspace), B images of PR x PC */
+    const float* thr;          /* the tensor's float32 threshold (null: none) */
+    unsigned long long* zc;    /* its record's zero count (null: not counted) */
+    int32_t B;                 /* images */
+    uint8_t H, W, L, nl_log2;
+};
+struct MTinyTable {
+    int32_t nseg, nwave, mode, F;
+    float f[4][MT_F_MAX];      /* dec_lo, dec_hi, rec_lo, rec_hi */
+    int32_t wave_begin[SEG_PER_LAUNCH];
+    MTinySeg s[SEG_PER_LAUNCH];
+};
+void launch_mtiny_fwd(const MTinyTable& t, hipStream_t s);
+void launch_mtiny_inv(const MTinyTable& t, hipStream_t s);
 /* 1-D flattened mode (one line per tensor) */
 void launch_dwt1_level(const float* x, int64_t N, const Taps& tp, float* a, float* d, hipStream_t s);
 void launch_idwt1_level(const float* a, int a_thr, const float* d, int64_t N, const Taps& tp, const float* thr,

@@ -13,8 +13,9 @@ module; the arithmetic runs in libwtprune.so (HIP, gfx950) on device-resident te
 Differences by design (documented in DESIGN.md): `wavelet_pruning` prunes every Conv2d of
 the model in ONE batched launch sequence instead of a per-layer loop (results and logs are
 identical); weights that live on the CPU are moved to the current CUDA device for the
-computation and the results are returned on the weight's own device; only
-mode='periodization' exists (the only mode the reference uses).
+computation and the results are returned on the weight's own device; of PyWavelets' modes
+periodization, zero, constant, symmetric, reflect and periodic exist (smooth, antisymmetric and
+antireflect raise NotImplementedError).
 """
 import os
 from typing import List, Tuple
@@ -80,10 +81,10 @@ def percentile_based_thresholding(coeff_arr, percentile=90):
     return out.to(dev)
 
 
-def _run(weights, wavelet, level, percentile, carry_level, verbose, flatten=False):
+def _run(weights, wavelet, level, percentile, carry_level, verbose, flatten=False, mode="periodization"):
     devs = [w.device for w in weights]
     dev_w = [_cuda(w.detach()) for w in weights]
-    outs, recs = engine.prune(dev_w, wavelet, level, percentile, carry_level=carry_level, flatten=flatten)
+    outs, recs = engine.prune(dev_w, wavelet, level, percentile, carry_level=carry_level, flatten=flatten, mode=mode)
     outs = [o.to(d) for o, d in zip(outs, devs)]
     if verbose:
         for r in recs:
@@ -110,13 +111,15 @@ def multi_resolution_analysis(weights: List[torch.Tensor], wavelet: str, level: 
     Returns (pruned tensors on their original devices, total count of exact zeros).
     flatten=True (an extension, not in the reference): the 1-D pywt.wavedec / waverec of every
     ndim >= 2 tensor's flattened weights instead of the 2-D transform over its last two axes
-    (WTP_FLATTEN, include/wtprune.h)."""
-    if mode != "periodization":
-        raise NotImplementedError("only mode='periodization' is implemented (the reference's only mode)")
+    (WTP_FLATTEN, include/wtprune.h).
+    mode: handed to pywt.wavedec2 / waverec2 by the reference (:67-68, :77); periodization, zero,
+    constant, symmetric, reflect and periodic run (wtp_prune_mode_f32), the modes PyWavelets has
+    beyond those raise NotImplementedError and any other name PyWavelets' ValueError."""
+    engine.mode_id(mode)
     if len(weights) == 0:
         return [], 0
     with torch.no_grad():
-        outs, recs = _run(list(weights), wavelet, level, percentile, True, verbose, flatten)
+        outs, recs = _run(list(weights), wavelet, level, percentile, True, verbose, flatten, mode)
     mism = _mismatches(weights, recs, flatten)
     if mism > 0:
         print(f"Warning: Shape mismatch occurred in {mism} weights")
@@ -125,12 +128,13 @@ def multi_resolution_analysis(weights: List[torch.Tensor], wavelet: str, level: 
 
 
 def prune_layer_weights(layer: nn.Module, wavelet: str, level: int, percentile: float,
-                        verbose: bool = True, flatten: bool = False) -> Tuple[int, int, int]:
+                        verbose: bool = True, flatten: bool = False, *,
+                        mode: str = "periodization") -> Tuple[int, int, int]:
     """Prune layer.weight in place (the bias is untouched); returns (numel, non-zero after,
     zero count) -- dwt_pruning.py:98-127."""
     with torch.no_grad():
         w = layer.weight
-        pruned, zero_count = multi_resolution_analysis([w], wavelet, level, percentile, verbose=verbose,
+        pruned, zero_count = multi_resolution_analysis([w], wavelet, level, percentile, mode=mode, verbose=verbose,
                                                        flatten=flatten)
         original = w.numel()
         nonzero = int(torch.count_nonzero(pruned[0]).item())
@@ -141,11 +145,13 @@ def prune_layer_weights(layer: nn.Module, wavelet: str, level: int, percentile: 
 
 
 def wavelet_pruning(model, wavelet: str, level: int, percentile: float, csv_path: str, guid: str,
-                    verbose: bool = True, flatten: bool = False) -> str:
+                    verbose: bool = True, flatten: bool = False, *, mode: str = "periodization") -> str:
     """Prune every Conv2d weight of `model`, log per layer, save the model and append the run
     to the experiment log; returns the per-layer log path (dwt_pruning.py:130-174).
     All layers go through ONE batched device launch sequence (each layer keeps its own
-    requested level, exactly as the reference's per-layer calls do)."""
+    requested level, exactly as the reference's per-layer calls do).  mode: as
+    multi_resolution_analysis (the directory name and the CSV schema do not record it)."""
+    engine.mode_id(mode)
     threshold_value = percentile / 100
     out_dir = check_and_set_pruned_instance_path(
         f"{wavelet}_threshold-{threshold_value}_level-{level}_guid-{guid[:4]}/selective_pruned")
@@ -156,7 +162,7 @@ def wavelet_pruning(model, wavelet: str, level: int, percentile: float, csv_path
     total_nonzero = 0
     with torch.no_grad():
         weights = [m.weight for _, m in convs]
-        outs, recs = _run(weights, wavelet, level, percentile, False, False, flatten) if convs else ([], [])
+        outs, recs = _run(weights, wavelet, level, percentile, False, False, flatten, mode) if convs else ([], [])
         for (name, m), out, rec in zip(convs, outs, recs):
             m.weight.data = out.to(dtype=m.weight.dtype).view(m.weight.shape)
             numel, zeros = rec["numel"], rec["zero_count"]

@@ -144,8 +144,24 @@ def check_tensors(tensors):
 WTP_CARRY_LEVEL, WTP_FLATTEN, WTP_NO_RESIDENT = 1, 2, 4  # include/wtprune.h
 
 
+MODES = ("periodization", "zero", "constant", "symmetric", "reflect", "periodic")  # WTP_MODE_* 0..5
+
+
+def mode_id(mode):
+    """WTP_MODE_* id of a PyWavelets mode name (include/wtprune.h).  A name pywt rejects raises
+    pywt's ValueError; smooth, antisymmetric and antireflect raise NotImplementedError."""
+    if mode == MODES[0]:
+        return 0
+    mid = N.lib().wtp_mode_id(mode.encode()) if isinstance(mode, str) else -1
+    if mid < 0:
+        raise ValueError("Unknown mode name '%s'." % (mode,))
+    if mid >= len(MODES):
+        raise NotImplementedError("mode=%r is not implemented (implemented: %s)" % (mode, ", ".join(MODES)))
+    return mid
+
+
 def launch(tensors, wavelet, level, pct, outs=None, carry_level=True, stream=None, flatten=False,
-           no_resident=False, results=None):
+           no_resident=False, results=None, mode="periodization"):
     """Enqueue the path for `tensors` (CUDA float32) on `stream` (default: current stream).
     Returns (outs, results_dev) without synchronising; results_dev is a uint8 CUDA tensor of
     len(tensors) wtp_result records.  carry_level=True is multi_resolution_analysis over a
@@ -153,7 +169,11 @@ def launch(tensors, wavelet, level, pct, outs=None, carry_level=True, stream=Non
     (prune_layer_weights / wavelet_pruning).  flatten=True: the 1-D flattened mode (WTP_FLATTEN).
     A record whose path reads MODE_FAULT was not computed (the resident launch's grid was not
     co-resident; nothing was stored for that tensor): prune() re-runs such tensors itself.
+    mode: the PyWavelets signal-extension mode of the transform (wtp_prune_mode_f32).
     results: optional uint8 CUDA tensor of len(tensors) records (8-byte aligned) to write into."""
+    mid = mode_id(mode)
+    if mid and flatten:
+        raise ValueError("wavelettransforms_amd: flatten=True runs under mode='periodization' only")
     check_tensors(tensors)
     tensors = [x.contiguous() for x in tensors]
     if outs is None:
@@ -169,7 +189,10 @@ def launch(tensors, wavelet, level, pct, outs=None, carry_level=True, stream=Non
     desc = _as_desc(tensors, outs)
     flags = ((WTP_CARRY_LEVEL if carry_level else 0) | (WTP_FLATTEN if flatten else 0)
              | (WTP_NO_RESIDENT if no_resident else 0))
-    nbytes = L.wtp_workspace_size_ex(desc, n, wid, int(level), flags)
+    if mid:
+        nbytes = L.wtp_workspace_size_mode(desc, n, wid, int(level), flags, mid)
+    else:
+        nbytes = L.wtp_workspace_size_ex(desc, n, wid, int(level), flags)
     if stream is None:
         stream = torch.cuda.current_stream(device)
     ws = workspace(device, nbytes if nbytes else 256, stream)
@@ -180,8 +203,12 @@ def launch(tensors, wavelet, level, pct, outs=None, carry_level=True, stream=Non
                 or results.data_ptr() % 8):
             raise ValueError("wavelettransforms_amd: results must be %d 8-byte aligned CUDA bytes" % (n * N.RESULT_BYTES))
         res = results
-    rc = L.wtp_prune_ex_f32(desc, n, wid, int(level), float(pct), flags, ws.data_ptr(), ws.numel(), res.data_ptr(),
-                            ctypes.c_void_p(stream.cuda_stream))
+    if mid:
+        rc = L.wtp_prune_mode_f32(desc, n, wid, int(level), float(pct), flags, mid, ws.data_ptr(), ws.numel(),
+                                  res.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    else:
+        rc = L.wtp_prune_ex_f32(desc, n, wid, int(level), float(pct), flags, ws.data_ptr(), ws.numel(), res.data_ptr(),
+                                ctypes.c_void_p(stream.cuda_stream))
     if rc != N.WTP_OK:
         raise_for(rc, tensors, wavelet)
     return outs, res
@@ -291,13 +318,13 @@ def resident_capacity():
     return int(N.lib().wtp_resident_capacity())
 
 
-def prune(tensors, wavelet, level, pct, outs=None, carry_level=True, flatten=False):
+def prune(tensors, wavelet, level, pct, outs=None, carry_level=True, flatten=False, mode="periodization"):
     """launch() + wait + decoded per-tensor records (numel, zero_count, nonzero, thr64, ...).
     Tensors whose resident launch faulted (their inputs and outputs untouched) are re-run once in
     the three-launch form -- only those: a tensor pruned in place must not be pruned twice.  Under
     carry_level each one re-runs at the level the list carried into it (computed from the shapes
     of the tensors before it), as an independent call, grouped by that level."""
-    outs, res = launch(tensors, wavelet, level, pct, outs=outs, carry_level=carry_level, flatten=flatten)
+    outs, res = launch(tensors, wavelet, level, pct, outs=outs, carry_level=carry_level, flatten=flatten, mode=mode)
     if res is None:
         return outs, []
     n = len(tensors)
@@ -311,7 +338,7 @@ def prune(tensors, wavelet, level, pct, outs=None, carry_level=True, flatten=Fal
         merged = res.clone().view(n, N.RESULT_BYTES)
         for lvl, g in groups.items():
             _, res2 = launch([tensors[i] for i in g], wavelet, lvl, pct, outs=[outs[i] for i in g],
-                             carry_level=False, flatten=flatten, no_resident=True)
+                             carry_level=False, flatten=flatten, no_resident=True, mode=mode)
             merged[g] = res2.view(len(g), N.RESULT_BYTES)
         res = merged.view(-1)
     return outs, decode(res, n)
@@ -504,6 +531,52 @@ def waverec2_packed(P, shape, wavelet, level, thr32=None):
     rc = L.wtp_waverec2_f32(P.contiguous().data_ptr(), out.data_ptr(), B, H, W, wavelet_id(wavelet), int(level),
                             thr.data_ptr() if thr is not None else None, ws.data_ptr(), ws.numel(),
                             ctypes.c_void_p(torch.cuda.current_stream(P.device).cuda_stream))
+    if rc != 0:
+        raise_for(rc, [P], wavelet)
+    return out
+
+
+def wavedec2_packed_mode(x, wavelet, level, mode):
+    """pywt.coeffs_to_array(pywt.wavedec2(x, wavelet, mode, level, axes=(-2,-1)))[0] on the GPU
+    (wtp_wavedec2_mode_f32: the level as given, padding cells zero)."""
+    mid = mode_id(mode)
+    check_tensors([x])
+    x = x.contiguous()
+    L = N.lib()
+    wid = wavelet_id(wavelet)
+    H, W = x.shape[-2], x.shape[-1]
+    B = x.numel() // max(1, H * W)
+    pr, pc = ctypes.c_int64(), ctypes.c_int64()
+    if L.wtp_packed_shape_mode(H, W, wid, int(level), mid, ctypes.byref(pr), ctypes.byref(pc)) != 0:
+        raise ValueError(N.last_error())
+    P = torch.empty(tuple(x.shape[:-2]) + (pr.value, pc.value), dtype=torch.float32, device=x.device)
+    nb = L.wtp_dwt_workspace_size_mode(B, H, W, wid, int(level), mid)
+    ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=x.device)
+    rc = L.wtp_wavedec2_mode_f32(x.data_ptr(), P.data_ptr(), B, H, W, wid, int(level), mid, ws.data_ptr(), ws.numel(),
+                                 ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+    if rc != 0:
+        raise_for(rc, [x], wavelet)
+    return P
+
+
+def waverec2_packed_mode(P, shape, wavelet, level, mode, thr32=None):
+    """array_to_coeffs + waverec2(mode) + crop to `shape` (optionally thresholding on load)."""
+    mid = mode_id(mode)
+    L = N.lib()
+    wid = wavelet_id(wavelet)
+    H, W = shape[-2], shape[-1]
+    B = 1
+    for s in shape[:-2]:
+        B *= s
+    out = torch.empty(tuple(shape), dtype=torch.float32, device=P.device)
+    nb = L.wtp_dwt_workspace_size_mode(B, H, W, wid, int(level), mid)
+    ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=P.device)
+    thr = None
+    if thr32 is not None:
+        thr = torch.tensor([thr32], dtype=torch.float32, device=P.device)
+    rc = L.wtp_waverec2_mode_f32(P.contiguous().data_ptr(), out.data_ptr(), B, H, W, wid, int(level), mid,
+                                 thr.data_ptr() if thr is not None else None, ws.data_ptr(), ws.numel(),
+                                 ctypes.c_void_p(torch.cuda.current_stream(P.device).cuda_stream))
     if rc != 0:
         raise_for(rc, [P], wavelet)
     return out
