@@ -7,6 +7,7 @@
 //   1 mode F N | taps[4F] | x[N]                  -> M | a[M] d[M] | K | y[K]   (dwt, idwt)
 //   2 mode F H W L                                 -> R[0..L] C[0..L] PR PC outH outW
 //   3 mode F B H W L thr | taps[4F] | x[B H W]     -> PR PC | packed[B PR PC] | out[B H W]
+//   4 H W L F                                      -> wtm_tiny_lanes_log2 (-1: not a tiny tensor)
 // Record 3 is wavedec2 + coeffs_to_array, np.where(|c| < thr, 0, c), waverec2 and the crop to
 // H x W, level by level as the kernels of csrc/modes.hip run them.
 #include <cmath>
@@ -140,6 +141,13 @@ static bool rec_image() {
     return true;
 }
 
+static bool rec_lanes() {
+    if (!have(4)) return false;
+    const int H = rd_i(), W = rd_i(), L = rd_i(), F = rd_i();
+    wr_i((int32_t)wtm_tiny_lanes_log2(H, W, L, F));
+    return true;
+}
+
 int main(int argc, char** argv) {
     if (argc != 3) return 2;
     FILE* fi = fopen(argv[1], "rb");
@@ -156,7 +164,7 @@ int main(int argc, char** argv) {
     int n = 0;
     while (g_pos < g_in.size()) {
         const int kind = rd_i();
-        const bool ok = kind == 1 ? rec_line() : kind == 2 ? rec_geom() : kind == 3 ? rec_image() : false;
+        const bool ok = kind == 1 ? rec_line() : kind == 2 ? rec_geom() : kind == 3 ? rec_image() : kind == 4 ? rec_lanes() : false;
         if (!ok) {
             fprintf(stderr, "modescore: bad record %d (kind %d)\n", n, kind);
             fclose(g_out);

@@ -5,20 +5,15 @@ and the whole wavedec2 -> threshold -> waverec2 -> crop of the golden cases leve
 import hashlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests.modes_ref import MODE_ID, MODES, build as _build, run as _run
 from wavelettransforms_amd import workloads as W
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-BUILD = os.path.join(HERE, "_build")
-SRC = os.path.join(HERE, "native", "modescore.cpp")
-CSRC = os.path.join(HERE, "..", "wavelettransforms_amd", "csrc")
-MODE_ID = {"periodization": 0, "zero": 1, "constant": 2, "symmetric": 3, "reflect": 4, "periodic": 5}
-MODES = ["zero", "constant", "symmetric", "reflect", "periodic"]
 SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
 
 
@@ -27,26 +22,6 @@ def golden():
     with open(os.path.join(HERE, "golden", "modes_manifest.json")) as fh:
         man = json.load(fh)
     return man, np.load(os.path.join(HERE, "golden", "modes_cases.npz"))
-
-
-def _build(name, flags):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, name)
-    deps = [SRC, os.path.join(CSRC, "wt_modes_core.h"), os.path.join(CSRC, "wt_dwt_core.h")]
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off"] + flags + ["-o", exe, SRC])
-    return exe
-
-
-def _run(exe, words, tag):
-    fin, fout = os.path.join(BUILD, tag + ".in"), os.path.join(BUILD, tag + ".out")
-    np.concatenate([np.asarray(w).reshape(-1).view(np.uint32) for w in words]).tofile(fin)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1:verify_asan_link_order=0",
-               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")  # as tests/test_sanitizers.py
-    p = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=env, timeout=600)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
-    assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr, p.stderr[-4000:]
-    return np.fromfile(fout, np.uint32)
 
 
 def _i(*v):
