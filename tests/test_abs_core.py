@@ -65,7 +65,7 @@ def test_image_routine_matches_oracle(core, wavelet):
 
 
 def test_planner_lane_choice(core):
-    """abs_lanes_log2 is what plan_abs (csrc/api.hip) calls: 64 images a wave while their areas
+    """abs_lanes_log2 is what plan_abs (csrc/host_methods.hip) calls: 64 images a wave while their areas
     fit the arena (16 KB less the wave's copy of the four filters), else the next power of two
     that fits; a side above 8 is not a tiny image."""
     assert core.abs_core_wave_words() == 4096 - 4 * 102 == 3688

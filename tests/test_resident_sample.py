@@ -1,4 +1,4 @@
-"""k_resident's sample positions (csrc/resident.inc res_body P0, host csrc/api.hip res_step_fx):
+"""k_resident's sample positions (csrc/resident.inc res_body P0, host csrc/host_prune.hip res_step_fx):
 group g of SAMPLE_GROUP contiguous keys starts at floor(g (n - 16) / 255), computed on the device
 as floor(g * step_fx / 2^32) from a 32.32 fixed-point step the host rounds up.  Restated here
 over many segment sizes: every start is the exact floor and every position lies in [0, n)."""
@@ -8,7 +8,7 @@ RES_MS, SAMPLE_GROUP = 4096, 16
 D = RES_MS // SAMPLE_GROUP - 1
 
 
-def step_fx(n):  # csrc/api.hip: rounded up
+def step_fx(n):  # csrc/host_prune.hip, build_seg_table: rounded up
     return (((n - SAMPLE_GROUP) << 32) + (D - 1)) // D
 
 

@@ -20,7 +20,12 @@ __device__ unsigned long long g_sprobe[NWG][16];
 #include "filterbank.hip"  /* -I wavelettransforms_amd/csrc (or a variant copy) */
 #include "small.hip"  /* -I wavelettransforms_amd/csrc (or a variant copy) */
 #include "abs.hip"
-#include "api.hip"  /* -I wavelettransforms_amd/csrc (or a variant copy) */
+#include "modes.hip"
+#include "host_plan.hip"  /* the host units: they compile as one file too (no file-local name twice) */
+#include "host_chains.hip"
+#include "host_prune.hip"
+#include "host_methods.hip"
+#include "host_query.hip"
 #include <cstdio>
 #include <vector>
 #include <algorithm>

@@ -18,10 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(OUT_DIR, "libwtprune.so")
-SOURCES = ["prune_unit.hip", "filterbank.hip", "small.hip", "abs.hip", "modes.hip", "api.hip"]
-DEPS = SOURCES + ["select.inc", "resident.inc", "levels.inc", "randprune.inc", "wtp_internal.h", "wtp_device.h",
-                  "wtp_select.h", "wt_dwt_core.h", "wt_abs_core.h", "wt_modes_core.h", "wt_synth.h",
-                  "wt_perm.h", "wt_filters.inc", "small_geom.h", "fb_index.h"]
+SOURCES = ["prune_unit.hip", "filterbank.hip", "small.hip", "abs.hip", "modes.hip",
+           "host_plan.hip", "host_chains.hip", "host_prune.hip", "host_methods.hip", "host_query.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("WTP_OFFLOAD_ARCH", "gfx950")
 
@@ -33,7 +31,8 @@ def stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, d) for d in DEPS] + [os.path.join(os.path.dirname(HERE), "include", "wtprune.h")]
+    # every file of csrc/ is a dependency: a new header or .inc cannot be forgotten
+    deps = glob.glob(os.path.join(CSRC, "*")) + [os.path.join(os.path.dirname(HERE), "include", "wtprune.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
