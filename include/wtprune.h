@@ -18,6 +18,8 @@
  *   wtp_waverec2_f32                array_to_coeffs + waverec2 + crop dwt_pruning.py:75-82
  *   wtp_prune_mode_f32              multi_resolution_analysis(mode=)  dwt_pruning.py:35, :67-68, :77
  *   wtp_prune_abs_f32               multi_resolution_analysis         dwt_pruning_NoEntropy.py:29-60
+ *   wtp_prune_sweep_f32             multi_resolution_analysis at a grid of percentiles: the loop of
+ *                                   main_pruning.py:186 over its thresholds, in one call
  *   wtp_synth_f32                   (test/bench input generator, no reference counterpart)
  */
 #ifndef WTPRUNE_H
@@ -212,6 +214,42 @@ typedef struct wtp_abs_result {   /* one per tensor, device memory */
 size_t wtp_abs_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level);
 int wtp_prune_abs_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double threshold,
                       void* workspace, size_t workspace_bytes, wtp_abs_result* results_dev, wtp_stream_t stream);
+
+/* ---- the percentile sweep: one call prunes the list at several percentiles (the experiment of
+ * ResNet/main_pruning.py:186, the same model and wavelet at a grid of thresholds) ----
+ * For every k < npct the outputs outs[k * ntensors + t] and the records results_dev[k * ntensors + t]
+ * (percentile-major: block k of the records is laid out like the records of one ordinary call)
+ * are, bit for bit and field for field, what wtp_prune_ex_f32(tensors, ..., pcts[k],
+ * flags & WTP_CARRY_LEVEL, ...) gives under periodization, except that path reads WTP_PATH_SWEEP:
+ * the level clamp and its carry, the ndim < 2 branch, padding zeros of a packed array that is not
+ * tight, NumPy 1.x's lerp, the float32 compare, the NaN rule, the crops and their WTP_ECROP cases.
+ * The forward transform runs once, one exact selection finds the order statistics of all the
+ * percentiles (three histogram passes over the population whatever npct is; tie-heavy populations
+ * cost the same), then every percentile's mask or inverse transform writes its output.
+ * tensors[t].out is ignored and may be NULL.  pcts (host memory) may hold duplicates and need
+ * not be sorted: every k is answered on its own.
+ * flags: WTP_CARRY_LEVEL as elsewhere; WTP_SWEEP_THRESHOLDS_ONLY stops after the selection: the
+ * records carry every field with zero_count = 0, outs may be NULL and no output is written.
+ * WTP_FLATTEN, WTP_NO_RESIDENT and any other bit are WTP_EARG; periodization only.
+ * Validation before any device work, nothing written on error: everything wtp_prune_ex_f32
+ * rejects, and npct outside [1, WTP_SWEEP_MAX_PCT] or pcts == NULL (WTP_EARG), a pcts[k] outside
+ * [0, 100] or NaN (WTP_EBADPCT), a NULL output pointer without WTP_SWEEP_THRESHOLDS_ONLY
+ * (WTP_EARG), two outputs of one tensor at the same address (WTP_EARG).  AT MOST ONE output of a
+ * tensor may be the tensor's input (in place); the other outputs must not overlap it.
+ * Workspace: wtp_sweep_workspace_size bytes (0 if the request is invalid).  It needs no
+ * initialisation (the call's first kernel zeroes what it accumulates into) and is plain scratch
+ * of this entry alone: like the absolute-threshold workspace it MUST NOT be the workspace of
+ * wtp_prune*_f32 / wtp_threshold_f32 / wtp_min_prune_f32.  Stream-ordered on the caller's stream
+ * only, no allocation, no synchronisation, capturable. */
+#define WTP_SWEEP_MAX_PCT 8
+#define WTP_SWEEP_THRESHOLDS_ONLY 16 /* a flag of this entry only */
+#define WTP_PATH_SWEEP 5
+size_t wtp_sweep_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int npct,
+                                int flags);
+int wtp_prune_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level,
+                        const double* pcts /* host */, int npct, int flags,
+                        float* const* outs /* host array of npct * ntensors device pointers */, void* workspace,
+                        size_t workspace_bytes, wtp_result* results_dev /* npct * ntensors */, wtp_stream_t stream);
 
 /* percentile_based_thresholding(arr, pct) on n device floats: out = where(|in| < thr, 0, in) */
 int wtp_threshold_f32(const float* in, float* out, int64_t n, double pct, void* workspace,

@@ -18,8 +18,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(OUT_DIR, "libwtprune.so")
-SOURCES = ["prune_unit.hip", "filterbank.hip", "small.hip", "abs.hip", "modes.hip",
-           "host_plan.hip", "host_chains.hip", "host_prune.hip", "host_methods.hip", "host_query.hip"]
+SOURCES = ["prune_unit.hip", "filterbank.hip", "small.hip", "abs.hip", "modes.hip", "sweep.hip",
+           "host_plan.hip", "host_chains.hip", "host_prune.hip", "host_methods.hip", "host_query.hip",
+           "host_sweep.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("WTP_OFFLOAD_ARCH", "gfx950")
 

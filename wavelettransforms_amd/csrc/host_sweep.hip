@@ -1,0 +1,205 @@
+/*
+ * host_sweep.hip -- the percentile sweep (wtp_prune_sweep_f32): plan_tensors' plan, one forward
+ * transform per tensor, one selection of every percentile's order statistics (sweep.hip), then per
+ * percentile the level-0 mask or the inverse transform.  Workspace: [SwState per tensor | the
+ * float32 threshold words (npct x ntensors) | pass-1 histograms | pass-2 and pass-3 slot
+ * histograms | a packed array per transformed tensor | three level temps per launch-group slot].
+ */
+#include "wtp_host.h"
+
+using namespace wtp;
+
+namespace {
+
+struct SweepPlan {
+    std::vector<TPlan> ps;
+    size_t st = 0, thr = 0, h1 = 0, h2 = 0, h3 = 0, zero_end = 0, total = 0;
+};
+
+bool sweep_flags_ok(int flags) { return !(flags & ~(WTP_CARRY_LEVEL | WTP_SWEEP_THRESHOLDS_ONLY)); }
+bool pct_bad(double p) { return !(p >= 0.0 && p <= 100.0); }
+
+/* the plan of plan_tensors (validated with percentile `pct`) and this entry's layout */
+int plan_sweep(const wtp_tensor* ts, int n, int wid, int level, double pct, int npct, bool carry, SweepPlan& sp) {
+    const int rc = plan_tensors(ts, n, wid, level, pct, false, sp.ps, carry, false, WTP_MODE_PERIODIZATION);
+    if (rc != WTP_OK) return rc;
+    const Taps tp = taps_for(wid);
+    size_t off = 0;
+    sp.st = off;
+    off = align_up(off + (size_t)n * sizeof(SwState));
+    sp.h1 = off;
+    off = align_up(off + (size_t)n * SW_BINS1 * sizeof(uint32_t));
+    sp.h2 = off;
+    off = align_up(off + (size_t)n * SW_SLOT_WORDS * sizeof(uint32_t));
+    sp.h3 = off;
+    off = align_up(off + (size_t)n * SW_SLOT_WORDS * sizeof(uint32_t));
+    sp.zero_end = off; /* k_sweep_init zeroes [st, zero_end) */
+    sp.thr = off;
+    off = align_up(off + (size_t)npct * n * sizeof(float));
+    for (auto& p : sp.ps) {
+        if (!p.dwt) continue;
+        p.p_off = off;
+        off = align_up(off + (size_t)p.pop * sizeof(float));
+    }
+    /* level temps per launch-group slot: the groups run one after another on the stream */
+    size_t slot_elems[SEG_PER_LAUNCH] = {};
+    for (size_t t = 0; t < sp.ps.size(); ++t)
+        if (sp.ps[t].dwt)
+            slot_elems[t % SEG_PER_LAUNCH] = std::max(slot_elems[t % SEG_PER_LAUNCH], temp_elems(sp.ps[t], tp));
+    size_t slot_off[SEG_PER_LAUNCH] = {};
+    for (int j = 0; j < SEG_PER_LAUNCH; ++j) {
+        if (!slot_elems[j]) continue;
+        slot_off[j] = off;
+        off = align_up(off + 3 * align_up(slot_elems[j] * sizeof(float)));
+    }
+    for (size_t t = 0; t < sp.ps.size(); ++t) {
+        if (!sp.ps[t].dwt) continue;
+        sp.ps[t].t_off = slot_off[t % SEG_PER_LAUNCH];
+        sp.ps[t].t_elems = slot_elems[t % SEG_PER_LAUNCH];
+    }
+    sp.total = off;
+    return WTP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t wtp_sweep_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int npct,
+                                int flags) {
+    if (ntensors < 0 || (ntensors > 0 && !tensors) || !sweep_flags_ok(flags) || npct < 1 || npct > WTP_SWEEP_MAX_PCT)
+        return 0;
+    SweepPlan sp;
+    if (plan_sweep(tensors, ntensors, wavelet_id, level, 50.0, npct, (flags & WTP_CARRY_LEVEL) != 0, sp) != WTP_OK)
+        return 0;
+    return sp.total;
+}
+
+int wtp_prune_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, const double* pcts,
+                        int npct, int flags, float* const* outs, void* ws, size_t ws_bytes, wtp_result* results,
+                        wtp_stream_t stream) {
+    clear_error();
+    if (ntensors < 0 || (ntensors > 0 && (!tensors || !results))) return fail(WTP_EARG, -1, "bad arguments");
+    if (!sweep_flags_ok(flags)) return fail(WTP_EARG, -1, "bad flags 0x%x", flags);
+    if (npct < 1 || npct > WTP_SWEEP_MAX_PCT || !pcts)
+        return fail(WTP_EARG, -1, "a sweep takes 1 to %d percentiles", WTP_SWEEP_MAX_PCT);
+    const bool thr_only = (flags & WTP_SWEEP_THRESHOLDS_ONLY) != 0;
+    const int n = ntensors;
+    /* a bad percentile among good ones: plan_tensors reports it where the reference would */
+    double vpct = pcts[0];
+    for (int k = npct - 1; k >= 0; --k)
+        if (pct_bad(pcts[k])) vpct = pcts[k];
+    if (n == 0) return pct_bad(vpct) ? fail(WTP_EBADPCT, -1, "Percentiles must be in the range [0, 100]") : WTP_OK;
+    SweepPlan sp;
+    int rc = plan_sweep(tensors, n, wavelet_id, level, vpct, npct, (flags & WTP_CARRY_LEVEL) != 0, sp);
+    if (rc != WTP_OK) return rc;
+    if (!thr_only && !outs) return fail(WTP_EARG, -1, "outs is NULL without WTP_SWEEP_THRESHOLDS_ONLY");
+    for (int t = 0; t < n; ++t) {
+        if (!tensors[t].in) return fail(WTP_EARG, t, "tensor %d: null pointer", t);
+        if (thr_only) continue;
+        for (int k = 0; k < npct; ++k) {
+            if (!outs[(size_t)k * n + t]) return fail(WTP_EARG, t, "tensor %d: output %d is a null pointer", t, k);
+            for (int j = 0; j < k; ++j)
+                if (outs[(size_t)j * n + t] == outs[(size_t)k * n + t])
+                    return fail(WTP_EARG, t, "tensor %d: outputs %d and %d are the same buffer", t, j, k);
+        }
+    }
+    if (!ws || ws_bytes < sp.total)
+        return fail(WTP_EWORKSPACE, -1, "workspace too small: need %zu bytes, got %zu", sp.total, ws_bytes);
+
+    const hipStream_t s = (hipStream_t)stream;
+    const Taps tp = taps_for(wavelet_id);
+    const SwWs w{wsb<SwState>(ws, sp.st), wsb<uint32_t>(ws, sp.h1), wsb<uint32_t>(ws, sp.h2), wsb<uint32_t>(ws, sp.h3),
+                 wsb<float>(ws, sp.thr)};
+    /* the states and histograms the passes accumulate into: zeroed by a kernel (a memset node
+     * misbehaved in a replayed graph: k_abs_init's note) */
+    launch_sweep_init(wsb<uint32_t>(ws, sp.st), (int64_t)((sp.zero_end - sp.st) / sizeof(uint32_t)), s);
+
+    const int ngroups = (n + SEG_PER_LAUNCH - 1) / SEG_PER_LAUNCH;
+    for (int gi = 0; gi < ngroups; ++gi) {
+        const int g0 = gi * SEG_PER_LAUNCH, g1 = std::min(n, g0 + SEG_PER_LAUNCH);
+        /* 1. the populations: pywt.wavedec2 + coeffs_to_array of the transformed tensors, once */
+        std::vector<Chain> fwd;
+        for (int t = g0; t < g1; ++t) {
+            const TPlan& p = sp.ps[t];
+            if (!p.dwt) continue;
+            float* P = wsb<float>(ws, p.p_off);
+            if (!p.tight) launch_abs_zero(P, p.pop, s);
+            fwd.push_back(make_chain(p, tensors[t].in, nullptr, P, wsb(ws, p.t_off), align_up(p.t_elems * sizeof(float)),
+                                     nullptr, nullptr));
+        }
+        if (!fwd.empty()) forward_chains(fwd, tp, s);
+        /* 2. the selection: three passes and their scans */
+        SwTable tab;
+        memset(&tab, 0, sizeof tab);
+        tab.npct = npct;
+        tab.ntensors = n;
+        int64_t chunks = 0;
+        for (int t = g0; t < g1; ++t) chunks += (sp.ps[t].pop + SW_CHUNK - 1) / SW_CHUNK;
+        tab.cpb = (int32_t)std::max<int64_t>(1, (chunks + SW_MAX_BLOCKS - 1) / SW_MAX_BLOCKS);
+        for (int t = g0; t < g1; ++t) {
+            const TPlan& p = sp.ps[t];
+            SwSeg& sg = tab.s[tab.nseg];
+            sg.data = p.dwt ? wsb<const float>(ws, p.p_off) : tensors[t].in;
+            sg.n = p.pop;
+            sg.t = t;
+            sg.eff_level = p.L;
+            sg.numel = p.numel;
+            for (int k = 0; k < npct; ++k) {
+                SegDesc sd;
+                memset(&sd, 0, sizeof sd);
+                seg_ranks(p.pop, pcts[k], sd);
+                sg.r0[k] = (uint32_t)sd.r0;
+                sg.gamma[k] = sd.gamma;
+                if (sd.above) sg.above |= 1u << k;
+            }
+            tab.blk_begin[tab.nseg++] = tab.nblk;
+            const int64_t nch = (p.pop + SW_CHUNK - 1) / SW_CHUNK;
+            tab.nblk += (int32_t)((nch + tab.cpb - 1) / tab.cpb);
+        }
+        for (int i = tab.nseg; i < SEG_PER_LAUNCH; ++i) tab.blk_begin[i] = INT32_MAX;
+        for (int pass = 1; pass <= 3; ++pass) launch_sweep_pass(tab, pass, w, results, s);
+        if (thr_only) continue;
+        /* 3. the outputs: level-0 and ndim < 2 tensors in one mask launch for all percentiles ... */
+        SwMaskTable mt;
+        memset(&mt, 0, sizeof mt);
+        mt.npct = npct;
+        mt.ntensors = n;
+        for (int t = g0; t < g1; ++t) {
+            const TPlan& p = sp.ps[t];
+            if (p.dwt) continue;
+            SwMaskSeg& mg = mt.s[mt.nseg];
+            mg.data = tensors[t].in;
+            mg.n = p.numel;
+            mg.t = t;
+            uintptr_t bits = reinterpret_cast<uintptr_t>(tensors[t].in);
+            for (int k = 0; k < npct; ++k) {
+                mg.out[k] = outs[(size_t)k * n + t];
+                bits |= reinterpret_cast<uintptr_t>(mg.out[k]);
+            }
+            mg.aligned = (bits & 15) == 0;
+            mt.blk_begin[mt.nseg++] = mt.nblk;
+            mt.nblk += (int32_t)((p.numel + SW_CHUNK - 1) / SW_CHUNK);
+        }
+        for (int i = mt.nseg; i < SEG_PER_LAUNCH; ++i) mt.blk_begin[i] = INT32_MAX;
+        if (mt.nseg) launch_sweep_mask(mt, w.thr, results, s);
+        /* ... the others by waverec2 of the same packed array, once per percentile, with that
+         * percentile's threshold word and zero counter */
+        if (fwd.empty()) continue;
+        for (int k = 0; k < npct; ++k) {
+            std::vector<Chain> inv;
+            for (int t = g0; t < g1; ++t) {
+                const TPlan& p = sp.ps[t];
+                if (!p.dwt) continue;
+                const size_t ri = (size_t)k * n + t;
+                inv.push_back(make_chain(p, tensors[t].in, outs[ri], wsb<float>(ws, p.p_off), wsb(ws, p.t_off),
+                                         align_up(p.t_elems * sizeof(float)), w.thr + ri,
+                                         reinterpret_cast<unsigned long long*>(&results[ri].zero_count)));
+            }
+            inverse_chains(inv, tp, s);
+        }
+    }
+    return check_launch();
+}
+
+}  // extern "C"

@@ -10,6 +10,7 @@
 #include "wt_dwt_core.h"
 #include "wt_abs_core.h"
 #include "wt_modes_core.h"
+#include "wt_sweep_core.h"
 
 #pragma clang fp contract(off)
 
@@ -518,6 +519,72 @@ struct MTinyTable {
 };
 void launch_mtiny_fwd(const MTinyTable& t, hipStream_t s);
 void launch_mtiny_inv(const MTinyTable& t, hipStream_t s);
+/* ---- the percentile sweep (sweep.hip, wtp_prune_sweep_f32; index arithmetic: wt_sweep_core.h) ----
+ * Per tensor of the call: a SwState, one pass-1 histogram and SW_MAX_RANKS slot histograms for each
+ * of the passes 2 and 3, all zeroed by the call's first launch (k_sweep_init). */
+constexpr int SW_THREADS = 256;
+constexpr int SW_SCAN_THREADS = 64 * SW_MAX_RANKS; /* k_sweep_scan: a wave per slot */
+constexpr int SW_CHUNK = CHUNK;          /* 16 float4 per thread */
+constexpr int SW_SLOT_WORDS = SW_MAX_RANKS * SW_BINS;
+constexpr int SW_MAX_BLOCKS = 256;       /* workgroups of a pass: each takes as many chunks as that needs (ResNet-18
+                                          * level-0 list, thresholds only: 1024 / 512 / 256 -> 115 / 109 / 103 us) */
+struct SwState {
+    uint32_t maxkey;                      /* pass 1: atomicMax of the keys */
+    uint32_t nslots[2];                   /* slots of pass 2, of pass 3 */
+    uint32_t pad;
+    uint32_t slot_prefix[2][SW_MAX_RANKS]; /* pass 2: the slot's top digit; pass 3: its 21-bit prefix */
+    uint32_t rank_prefix[SW_MAX_RANKS];   /* what the scans so far know of every rank's key */
+    uint32_t rank_res[SW_MAX_RANKS];      /* its rank among the keys with that prefix */
+    uint8_t rank_slot[SW_MAX_RANKS];      /* its slot in the coming pass */
+};
+static_assert(sizeof(SwState) % 16 == 0, "SwState array");
+struct SwSeg {
+    const float* data; /* the population: the tensor's input, or its packed array */
+    int64_t n;
+    int32_t t;         /* tensor index of the call: its SwState, histograms and records */
+    int32_t eff_level;
+    int64_t numel;
+    uint32_t r0[SW_MAX_PCT];   /* seg_ranks per percentile */
+    double gamma[SW_MAX_PCT];
+    uint32_t above;            /* bit k: percentile k's two order statistics are both the maximum */
+    int32_t pad;
+};
+struct SwTable {
+    int32_t nseg, nblk;
+    int32_t cpb;       /* chunks per workgroup */
+    int32_t npct;
+    int32_t ntensors;  /* of the call: record and threshold word (k, t) sit at k * ntensors + t */
+    int32_t pad;
+    int32_t blk_begin[SEG_PER_LAUNCH]; /* INT32_MAX past nseg */
+    SwSeg s[SEG_PER_LAUNCH];
+};
+static_assert(sizeof(SwTable) <= 4096, "the sweep kernels' argument");
+struct SwMaskSeg {
+    const float* data;
+    float* out[SW_MAX_PCT];
+    int64_t n;
+    int32_t t;
+    int32_t aligned;   /* data and every output 16-byte aligned */
+};
+struct SwMaskTable {
+    int32_t nseg, nblk, npct, ntensors;
+    int32_t blk_begin[SEG_PER_LAUNCH];
+    SwMaskSeg s[SEG_PER_LAUNCH];
+};
+static_assert(sizeof(SwMaskTable) <= 4096, "k_sweep_mask's argument");
+struct SwWs { /* the selection state's places in the workspace */
+    SwState* st;
+    uint32_t* h1;  /* SW_BINS1 words per tensor */
+    uint32_t* h2;  /* SW_SLOT_WORDS words per tensor */
+    uint32_t* h3;  /* " */
+    float* thr;    /* npct * ntensors float32 thresholds */
+};
+void launch_sweep_init(uint32_t* words, int64_t nwords, hipStream_t s);
+/* pass 1..3 over the launch group's populations, then that pass's scan; the third scan also
+ * writes the records (zero_count = 0) and the threshold words */
+void launch_sweep_pass(const SwTable& t, int pass, const SwWs& w, wtp_result* res, hipStream_t s);
+void launch_sweep_mask(const SwMaskTable& t, const float* thr, wtp_result* res, hipStream_t s);
+
 /* 1-D flattened mode (one line per tensor) */
 void launch_dwt1_level(const float* x, int64_t N, const Taps& tp, float* a, float* d, hipStream_t s);
 void launch_idwt1_level(const float* a, int a_thr, const float* d, int64_t N, const Taps& tp, const float* thr,

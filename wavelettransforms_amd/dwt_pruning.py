@@ -30,7 +30,7 @@ from .utils import (append_to_experiment_log, check_and_set_pruned_instance_path
                     save_model, setup_csv_writer)
 
 __all__ = ["calculate_max_level", "analyze_pruning", "percentile_based_thresholding",
-           "multi_resolution_analysis", "prune_layer_weights", "wavelet_pruning",
+           "multi_resolution_analysis", "multi_resolution_analysis_sweep", "prune_layer_weights", "wavelet_pruning",
            "prune_conv_layer", "apply_dwt_pruning"]
 
 
@@ -125,6 +125,33 @@ def multi_resolution_analysis(weights: List[torch.Tensor], wavelet: str, level: 
         print(f"Warning: Shape mismatch occurred in {mism} weights")
     outs = [o.to(dtype=w.dtype).view(w.shape) for o, w in zip(outs, weights)]
     return outs, int(sum(r["zero_count"] for r in recs))
+
+
+def multi_resolution_analysis_sweep(weights: List[torch.Tensor], wavelet: str, level: int,
+                                    percentiles) -> List[Tuple[List[torch.Tensor], int]]:
+    """multi_resolution_analysis at several percentiles in one device call (the reference's
+    experiment: main_pruning.py:186 runs the same model and wavelet at a grid of thresholds).
+    Returns a list over `percentiles` of (pruned tensors, total zero count), each entry what
+    multi_resolution_analysis(weights, wavelet, level, p) returns; the forward transform and the
+    selection run once for all of them (engine.prune_sweep; at most engine.WTP_SWEEP_MAX_PCT
+    percentiles a call, longer grids run in several).  The per-tensor threshold lines are not
+    printed."""
+    percentiles = list(percentiles)
+    if len(weights) == 0:
+        return [([], 0) for _ in percentiles]
+    weights = list(weights)
+    result = []
+    with torch.no_grad():
+        devs = [w.device for w in weights]
+        dev_w = [_cuda(w.detach()) for w in weights]
+        for i in range(0, len(percentiles), engine.WTP_SWEEP_MAX_PCT):
+            outs, recs = engine.prune_sweep(dev_w, wavelet, level, percentiles[i:i + engine.WTP_SWEEP_MAX_PCT])
+            for o, r in zip(outs, recs):
+                if _mismatches(weights, r) > 0:
+                    print(f"Warning: Shape mismatch occurred in {_mismatches(weights, r)} weights")
+                pruned = [y.to(d).to(dtype=w.dtype).view(w.shape) for y, d, w in zip(o, devs, weights)]
+                result.append((pruned, int(sum(x["zero_count"] for x in r))))
+    return result
 
 
 def prune_layer_weights(layer: nn.Module, wavelet: str, level: int, percentile: float,

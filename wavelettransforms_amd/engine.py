@@ -31,8 +31,8 @@ def workspace(device, nbytes, stream=None, kind=None):
     ever used keeps its workspace (at the largest size it needed: a cfg5-sized call holds the
     packed coefficients of its images) until release_workspaces() drops it.  kind=None is the
     workspace of the selection entries, whose state the library keeps clean; an entry that uses its
-    workspace as plain scratch (launch_abs: kind="abs") gets one of its own, so it never writes over
-    that state."""
+    workspace as plain scratch (launch_abs: kind="abs", launch_sweep: kind="sweep") gets one of its
+    own, so it never writes over that state."""
     device = torch.device(device)
     if device.index is None:
         device = torch.device(device.type, torch.cuda.current_device())
@@ -403,6 +403,70 @@ def prune_abs(tensors, wavelet, level, threshold, outs=None):
     if res is None:
         return outs, []
     return outs, decode_abs(res, len(tensors))
+
+
+WTP_SWEEP_MAX_PCT, WTP_SWEEP_THRESHOLDS_ONLY, MODE_SWEEP = 8, 16, 5  # include/wtprune.h
+
+
+def launch_sweep(tensors, wavelet, level, pcts, outs=None, carry_level=True, thresholds_only=False, stream=None):
+    """Enqueue the percentile sweep (wtp_prune_sweep_f32) for `tensors` (CUDA float32) on `stream`
+    (default: the current stream): one forward transform, one exact selection of every
+    percentile's order statistics, then each percentile's mask or inverse.  Returns (outs,
+    results_dev) without synchronising: outs[k][t] is tensor t pruned at pcts[k], bit for bit what
+    launch(tensors, wavelet, level, pcts[k], carry_level=carry_level) gives, and block k of
+    results_dev (len(tensors) wtp_result records) is that call's records with path == MODE_SWEEP.
+    outs: a list over the percentiles of output lists; at most one output of a tensor may be the
+    tensor itself.  thresholds_only=True stops after the selection: outs is None, the records
+    carry the thresholds with zero_count 0."""
+    pcts = [float(p) for p in pcts]
+    npct = len(pcts)
+    check_tensors(tensors)
+    tensors = [x.contiguous() for x in tensors]
+    if thresholds_only:
+        outs = None
+    elif outs is None:
+        outs = [[torch.empty_like(x) for x in tensors] for _ in range(npct)]
+    else:
+        if len(outs) != npct:
+            raise ValueError("wavelettransforms_amd: %d output sets for %d percentiles" % (len(outs), npct))
+        for o in outs:
+            check_outs(tensors, o)
+    n = len(tensors)
+    if n == 0:
+        return outs, None
+    device = tensors[0].device
+    L = N.lib()
+    wid = wavelet_id(wavelet)
+    desc = _as_desc(tensors, tensors)
+    flags = (WTP_CARRY_LEVEL if carry_level else 0) | (WTP_SWEEP_THRESHOLDS_ONLY if thresholds_only else 0)
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    nbytes = L.wtp_sweep_workspace_size(desc, n, wid, int(level), npct, flags)
+    # scratch of this entry alone: never the selection entries' workspace (include/wtprune.h)
+    ws = workspace(device, nbytes if nbytes else 256, stream, kind="sweep")
+    res = _results(max(1, npct) * n, device, stream)
+    parr = (ctypes.c_double * max(1, npct))(*pcts)
+    optr = None
+    if outs is not None:
+        optr = (ctypes.c_void_p * (npct * n))(*[y.data_ptr() if y.numel() else None for o in outs for y in o])
+    rc = L.wtp_prune_sweep_f32(desc, n, wid, int(level), parr, npct, flags, optr, ws.data_ptr(), ws.numel(),
+                               res.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    if rc != N.WTP_OK:
+        raise_for(rc, tensors, wavelet)
+    return outs, res
+
+
+def prune_sweep(tensors, wavelet, level, pcts, outs=None, carry_level=True, thresholds_only=False):
+    """launch_sweep() + wait + decoded records: (outs, recs) with recs[k][t] the record of tensor t
+    at pcts[k] (decode() of block k)."""
+    pcts = list(pcts)
+    outs, res = launch_sweep(tensors, wavelet, level, pcts, outs=outs, carry_level=carry_level,
+                             thresholds_only=thresholds_only)
+    npct, n = len(pcts), len(tensors)
+    if res is None:
+        return outs, [[] for _ in range(npct)]
+    blocks = res.view(npct, n * N.RESULT_BYTES)
+    return outs, [decode(blocks[k], n) for k in range(npct)]
 
 
 def min_prune(tensors, fraction, outs=None):
