@@ -3,13 +3,20 @@ k_inv_int): their tile decomposition, sample offsets, tap parities and the inter
 host computes (fwd_interior / inv_interior), restated in float64 NumPy loop for loop and compared
 with the C oracle's level-1 wavedec2 / waverec2 (pywt periodization) at every interior tile.  The
 GPU suite checks the kernels themselves bit for bit (tests/test_gpu_large_levels.py); this test
-catches an indexing slip without a GPU."""
+catches an indexing slip without a GPU.  The tile sizes come from the C++ (csrc/fb_plan.h through
+tests/native/fbplan.cpp), and the restated rectangles are held to the C++ ones over a sweep of
+levels, so what is compared with the oracle here is what the library's launchers compute."""
+import ctypes
+
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import fbplan_shim as S
 
-FR, FC, IR, IC = 16, 56, 64, 64  # filterbank.hip tile sizes
+_FB = S.load_shim()
+_C = S.consts(_FB)
+FR, FC, IR, IC = _C["FR"], _C["FC"], _C["IR"], _C["IC"]  # fb_plan.h tile sizes
 
 
 def _filters(wavelet):
@@ -33,7 +40,7 @@ def _syn_locate(n, N, F):  # wt_dwt_core.h wt_syn_locate
     return start + (n - 1) // 2, 1, False
 
 
-def _fwd_interior(R, C, F):  # filterbank.hip fwd_interior (al16 assumed)
+def _fwd_interior(R, C, F):  # fb_plan.h fwd_interior (al16 assumed)
     S0 = ((1 - F // 2) % 4 + 4) % 4
     TP = (S0 + 2 * FC + F - 2 + 3) // 4 * 4
     NR = 2 * FR + F - 2
@@ -45,7 +52,7 @@ def _fwd_interior(R, C, F):  # filterbank.hip fwd_interior (al16 assumed)
     return rows, cols
 
 
-def _inv_axis(out, N, F, T):  # filterbank.hip inv_axis
+def _inv_axis(out, N, F, T):  # fb_plan.h inv_axis
     H = F // 2
     ok = []
     for t in range((out + T - 1) // T):
@@ -61,6 +68,37 @@ def _inv_axis(out, N, F, T):  # filterbank.hip inv_axis
         ok.append(t)
     assert ok == list(range(ok[0], ok[-1] + 1)) if ok else True  # an interval
     return ok
+
+
+def _interval(ok):
+    return [1, ok[0], len(ok)] if ok else [0]
+
+
+@pytest.mark.parametrize("F", _C["spec"])
+def test_restated_rectangles_equal_the_library(F):
+    """_fwd_interior / _inv_axis against fb_plan.h's fwd_interior / inv_axis: every extent from 1 to a
+    few tile widths past two tiles, odd and even (the axes are independent, so each is swept
+    against a fixed other one)."""
+    q = (ctypes.c_int * 4)()
+    lo, cnt = ctypes.c_int(), ctypes.c_int()
+    rmax, cmax = 2 * (2 * FR) + 3 * (2 * FR), 2 * (2 * FC) + 3 * (2 * FC)  # inputs: a tile takes 2 T of them
+    shapes = [(R, C) for R in range(1, rmax) for C in (360, 261, 2 * FC + 2)]
+    shapes += [(R, C) for C in range(1, cmax) for R in (200, 75, 2 * FR + 2)]
+    for R, C in shapes:
+        rows, cols = _fwd_interior(R, C, F)
+        for al16 in (0, 1):  # the pitch may be aligned and the pointer not; C % 4 != 0 is never al16
+            if al16 and C % 4:
+                continue
+            has = _FB.fbp_fwd_interior(R, C, al16, 4 * ((R + 1) // 2) * ((C + 1) // 2), F, q)
+            assert bool(has) == bool(al16 and rows and cols), (R, C, al16)
+            if has:
+                assert list(q) == [rows[0], len(rows), cols[0], len(cols)], (R, C)
+    for T in (IR, IC):
+        for N in range(1, (2 * T + 3 * T) // 2):
+            for out in (2 * N - 1, 2 * N):
+                ok = _inv_axis(out, N, F, T)
+                has = _FB.fbp_inv_axis(T, out, N, F, ctypes.byref(lo), ctypes.byref(cnt))
+                assert ([1, lo.value, cnt.value] if has else [0]) == _interval(ok), (T, N, out)
 
 
 @pytest.mark.parametrize("wavelet", ["db2", "rbio2.2", "bior3.3", "db5", "db8", "db9"])

@@ -1,1 +1,1 @@
-filterbank.hip	s#constexpr int FR = 16, FC = 56;#constexpr int FR = 16, FC = 54;#
+fb_plan.h	s#constexpr int FR = 16, FC = 56;#constexpr int FR = 16, FC = 54;#
