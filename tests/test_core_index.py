@@ -1,33 +1,21 @@
 """CPU check of the product's gather-form filter-bank math (csrc/wt_dwt_core.h, compiled for
 the host here) against the oracle's literal scatter restatement and the pywt 1-D KATs."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests import corecheck_shim
 from tests import golden_io as G
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-SO = os.path.join(HERE, "_build", "libcorecheck.so")
 
 
 @pytest.fixture(scope="module")
 def core():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    src = os.path.join(HERE, "native", "corecheck.cpp")
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(
-            os.path.getmtime(src),
-            os.path.getmtime(os.path.join(HERE, "..", "wavelettransforms_amd", "csrc", "wt_dwt_core.h"))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC",
-                               "-o", SO, src])
-    return ctypes.CDLL(SO)
+    return corecheck_shim.load()
 
 
-def _p(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+_p = corecheck_shim.fptr
 
 
 def test_gather_matches_kat_and_oracle(core):

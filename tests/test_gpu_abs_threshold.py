@@ -15,12 +15,13 @@ import torch
 
 from oracle import oracle as O
 from tests import golden_io as G
+from tests.ref_helpers import ABS_CHAIN, ABS_MASK, ABS_TINY, abs_oracle
 
 pytestmark = pytest.mark.gpu
 
 ABS = json.load(open(os.path.join(G.GOLDEN, "abs_manifest.json")))
 ARR = dict(np.load(os.path.join(G.GOLDEN, "abs_cases.npz")))
-MASK, TINY, CHAIN = 0, 1, 2
+MASK, TINY, CHAIN = ABS_MASK, ABS_TINY, ABS_CHAIN
 
 
 @pytest.fixture(scope="module")
@@ -30,12 +31,7 @@ def eng():
     return engine
 
 
-def _oracle(x, wavelet, level, thr):
-    """The unchanged oracle as the yardstick (tests/test_abs_threshold_host.py pins it to the goldens)."""
-    thr32 = np.float32(thr)
-    if x.ndim < 2:
-        return np.where(np.abs(x) < thr32, np.float32(0), x)
-    return O.waverec2_packed(O.wavedec2_packed(x, wavelet, level), x.shape, wavelet, level, thr32)
+_oracle = abs_oracle
 
 
 def _zeroed_fraction(x, wavelet, level, thr):

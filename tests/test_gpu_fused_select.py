@@ -16,6 +16,7 @@ import torch
 
 from oracle import oracle as O
 from tests import golden_io as G
+from tests.ref_helpers import patch_origins
 
 pytestmark = pytest.mark.gpu
 
@@ -86,10 +87,7 @@ def test_fused_in_place(eng):
     _same(_run(eng, xs, True, "db8", 4, 50.0, in_place=True), _run(eng, xs, False, "db8", 4, 50.0))
 
 
-def _patch_origins(R, C):
-    """k_fwin's patch origins (csrc/select.inc): rows at 1/8, 3/8, 5/8, 7/8 and columns at 3/8,
-    7/8, 1/8, 5/8 of the free range, FWIN_PS = 128"""
-    return [((R - 128) * lr // 8, (C - 128) * lc // 8) for lr, lc in zip((1, 3, 5, 7), (3, 7, 1, 5))]
+_patch_origins = patch_origins
 
 
 @pytest.mark.timeout(300)

@@ -11,6 +11,7 @@ import torch
 
 from oracle import oracle as O
 from tests import golden_io as G
+from tests import special_values as SV
 from wavelettransforms_amd import _native as N
 from wavelettransforms_amd import engine as eng
 
@@ -92,8 +93,10 @@ def test_multi_tensor_carry_and_mixed_levels():
         _same(o.cpu().numpy(), ref, r, rr)
 
 
-@pytest.mark.parametrize("kind", ["constant", "zeros", "ties", "nan", "tiny", "huge"])
+@pytest.mark.parametrize("kind", ["constant", "zeros", "ties", "nan", "tiny", "huge", "inf", "negzero"])
 def test_degenerate_data(kind):
+    """inf and negzero are also compared word for word (special_values.assert_same_bits: the sign
+    of a zero counts, and no output of a transform is -0.0)"""
     rng = np.random.default_rng(7)
     x = rng.standard_normal((64, 96)).astype(np.float32)
     if kind == "constant":
@@ -108,11 +111,20 @@ def test_degenerate_data(kind):
         x *= np.float32(1e-39)  # subnormal coefficients
     elif kind == "huge":
         x *= np.float32(1e37)
+    elif kind == "inf":
+        x[40, 50] = np.inf
+        x[63, 95] = -np.inf
+    elif kind == "negzero":
+        x[10:40, 20:70] = np.float32(-0.0)
     for wavelet, pct in [("haar", 50.0), ("bior3.3", 37.5), ("db8", 12.5)]:
         ref, rr = O.prune_tensor(x, wavelet, 3, pct)
         outs, (r,) = _both([_dev(x)], wavelet, 3, pct)
         assert r["path"] == eng.MODE_SMALL
         _same(outs[0].cpu().numpy(), ref, r, rr)
+        if kind in ("inf", "negzero"):
+            SV.assert_same_bits(outs[0].cpu().numpy(), ref, (kind, wavelet))
+            SV.assert_same_record(r, rr, (kind, wavelet))
+            assert SV.neg_zero_words(ref) == 0 and SV.neg_zero_words(outs[0].cpu().numpy()) == 0
 
 
 @pytest.mark.parametrize("split", ["columns", "rows", "one_tile"])

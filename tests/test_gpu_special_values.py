@@ -1,0 +1,295 @@
+"""Special values through every transform path on the GPU: blocks of +0.0 and -0.0, a constant,
+subnormal and 2^126-sized input, NaN inside a tile and at the wrapping corner, +inf on the repeated
+sample of an odd extent and -inf inside, and weights scaled out of the fused window's bins
+(tests/special_values.py), against the C oracle -- and, for the extension modes, the fixture of
+tools/gen_golden_special_modes.py.  tests/test_special_values_ref.py shows on the CPU that the
+cases are not trivial and which kernels the shapes below reach.
+
+One comparison rule throughout (special_values.assert_same_bits): identical NaN masks, identical
+words everywhere else, so the sign of a zero counts.  It is applied to the output, to the packed
+array through wavedec2_packed where the level is at least 1, and to the record's thr64, thr32,
+max |c|; zero_count, eff_level and coeff_numel are compared exactly.  No transformed output and no
+packed coefficient may be -0.0 (pywt's sums start at +0), which is asserted on its own as well.
+
+  tiled     k_fwd_int / k_inv_int, their EDGE forms and the general kernels under set_interior
+            3, 2, 1 and 0: haar, bior3.3 (zero taps), db8, db9 (H odd) at (1, 2, 161, 464) level 2
+  generic   db10 (F = 20, the first generic tiled length), db17 (F = 34, the last tiled one) and
+            db18 (F = 36, the first per-point one); db38 (76 taps) and coif17 (102 taps)
+  small     (6, 4, 10, 12): images below the tiled kernels' 512 cells, the per-point kernels
+  fused     k_fwin and the forward's classification at 2048 x 2048, fused against unfused
+  abs       prune_abs: k_abs_tiny and the chain at unclamped levels
+  modes     k_mtiny_* and k_mdwt_* / k_midwt_* under the five extension modes
+  sweep     prune_sweep over transformed tensors
+The percentile calls run with no_resident=True so that the multi-launch form named above runs (a
+call this small is otherwise one launch of k_small), and once more as dispatched by default."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+from tests import golden_io as G
+from tests import special_values as SV
+from tests.ref_helpers import ABS_CHAIN as CHAIN, ABS_TINY as TINY, abs_oracle, patch_origins
+
+pytestmark = pytest.mark.gpu
+
+SHAPE, SEED, LEVEL, PCT = (1, 2, 161, 464), 97, 2, 61.8
+LONG_SHAPE, SMALL_SHAPE = (1, 1, 230, 470), (6, 4, 10, 12)
+MODES = ["zero", "constant", "symmetric", "reflect", "periodic"]
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from wavelettransforms_amd import engine
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return engine
+
+
+_inputs = {}
+
+
+def inputs(shape, tid=0):
+    """every case of special_values.cases and the plain base, built once per shape"""
+    key = (tuple(shape), tid)
+    if key not in _inputs:
+        cs = SV.cases(shape, SEED, tid)
+        cs["plain"] = SV.plain(shape, SEED, tid)
+        for a in cs.values():
+            a.setflags(write=False)
+        _inputs[key] = cs
+    return _inputs[key]
+
+
+def _ref(x, wavelet, level, pct):
+    with np.errstate(all="ignore"):
+        return O.prune_tensor(x, wavelet, level, pct, want_coeffs=True)
+
+
+def _dev(x):
+    return torch.from_numpy(np.array(x, np.float32)).cuda()
+
+
+def _check_out(out, r, ref, tag):
+    out_ref, rr, _ = ref
+    SV.assert_same_bits(out, out_ref, (tag, "out"))
+    SV.assert_same_record(r, rr, tag)
+    assert r["numel"] == out.size, tag
+    if rr["eff_level"] >= 1:
+        assert SV.neg_zero_words(out) == 0, (tag, "-0.0 in a transformed output")
+
+
+def _check_packed(eng, x, wavelet, ref, tag):
+    _, rr, P_ref = ref
+    assert rr["eff_level"] >= 1, tag
+    P = eng.wavedec2_packed(x, wavelet, rr["eff_level"]).cpu().numpy()
+    SV.assert_same_bits(P, P_ref, (tag, "packed"))
+    assert SV.neg_zero_words(P) == 0, (tag, "-0.0 in the packed array")
+
+
+def _prune_multi_launch(eng, x, wavelet, level, pct):
+    outs, res = eng.launch([x], wavelet, level, pct, carry_level=False, no_resident=True)
+    (r,) = eng.decode(res, 1)
+    assert r["path"] != eng.MODE_SMALL
+    return outs[0].cpu().numpy(), r
+
+
+def _percentile_cases(eng, shape, wavelet, level, names, eff, interior_modes=(None,)):
+    """each named case of `shape`: the multi-launch form under each interior mode (None: as set),
+    the packed array under each, and the call as dispatched by default, all against the oracle"""
+    cs = inputs(shape)
+    for name in names:
+        ref = _ref(cs[name], wavelet, level, PCT)
+        assert ref[1]["eff_level"] == eff, (wavelet, name)
+        x = _dev(cs[name])
+        for im in interior_modes:
+            prev = eng.set_interior(im) if im is not None else None
+            try:
+                tag = (wavelet, name, "interior", im)
+                out, r = _prune_multi_launch(eng, x, wavelet, level, PCT)
+                _check_out(out, r, ref, tag)
+                _check_packed(eng, x, wavelet, ref, tag)
+            finally:
+                if im is not None:
+                    eng.set_interior(prev)
+        outs, (r,) = eng.prune([x], wavelet, level, PCT, carry_level=False)
+        _check_out(outs[0].cpu().numpy(), r, ref, (wavelet, name, "default dispatch", r["path"]))
+        assert np.array_equal(x.cpu().numpy().view(np.uint32), cs[name].view(np.uint32)), "the input is untouched"
+
+
+@pytest.mark.parametrize("wavelet", ["haar", "bior3.3", "db8", "db9"])
+def test_tiled_filter_bank(eng, wavelet):
+    """Every case under set_interior 3, 2, 1 and 0, each mode against the oracle: interior tiles,
+    the frame in its EDGE form and in the general kernel, the one-launch edge form, threshold on
+    load, the packed f2 arithmetic and the fix-up passes."""
+    _percentile_cases(eng, SHAPE, wavelet, LEVEL, SV.NAMES + ["plain"], 2, interior_modes=(3, 2, 1, 0))
+
+
+@pytest.mark.parametrize("wavelet", ["db10", "db17", "db18"])
+def test_generic_tiled_and_per_point_at_the_length_boundary(eng, wavelet):
+    """F = 20 and 34 in the generic tiled kernels (inv_lds = 63 504 B of 65 536 at 34), F = 36 in the
+    per-point kernels of levels.inc: ordinary values and special ones."""
+    names = ["plain", "zero_blocks", "nan_corner", "infs", "huge"] + (["subnormal"] if wavelet == "db10" else [])
+    _percentile_cases(eng, SHAPE, wavelet, LEVEL, names, 2)
+
+
+@pytest.mark.parametrize("wavelet", ["coif17", "db38"])
+def test_longest_filters(eng, wavelet):
+    """102 and 76 taps, per-point, at the one level a 230-row image allows"""
+    _percentile_cases(eng, LONG_SHAPE, wavelet, 1, ["plain", "infs"], 1)
+
+
+@pytest.mark.parametrize("wavelet,level", [("haar", 2), ("db2", 1)])
+def test_small_images_per_point(eng, wavelet, level):
+    """24 images of 10 x 12: below the tiled kernels' 512 cells, every level per-point"""
+    _percentile_cases(eng, SMALL_SHAPE, wavelet, level, SV.NAMES + ["plain"], level)
+
+
+# ---- fused selection ----
+
+FUSED_SHAPE = (2048, 2048)
+
+
+def _fused_input(case):
+    if case in ("zero_blocks", "scaled_up", "scaled_down"):
+        return inputs(FUSED_SHAPE)[case]
+    x = np.array(inputs(FUSED_SHAPE)["plain"])
+    origins = patch_origins(*FUSED_SHAPE)
+    if case == "nan_in_patch":
+        r, c = origins[0][0] + 64, origins[0][1] + 64
+    else:  # outside every patch, more than a level-3 haar block away from each
+        r, c = 10, 10
+    inside = any(r0 <= r < r0 + 128 and c0 <= c < c0 + 128 for r0, c0 in origins)
+    near = any(r0 - 8 <= r < r0 + 136 and c0 - 8 <= c < c0 + 136 for r0, c0 in origins)
+    assert inside if case == "nan_in_patch" else not near
+    x[r, c] = np.nan
+    return x
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize("case", ["nan_in_patch", "nan_outside_patches", "zero_blocks", "scaled_up", "scaled_down"])
+def test_fused_selection(eng, case):
+    """A NaN the window's patches see and one only the forward's max key sees, blocks of zeros, and
+    coefficients all above / all below the window's bins [2^-26, 2^6): fused equals unfused equals
+    the oracle (the path is not pinned: a window that misses is selected again over the array)."""
+    x_np = _fused_input(case)
+    ref = _ref(x_np, "haar", 3, 50.0)
+    assert ref[1]["eff_level"] == 3
+    if case.startswith("nan"):
+        assert np.isnan(ref[1]["thr64"]) and 1 <= int(np.isnan(ref[0]).sum()) <= 64
+    x = _dev(x_np)
+    got = {}
+    for fused in (True, False):
+        prev = eng.set_fused_select(fused)
+        try:
+            outs, (r,) = eng.prune([x], "haar", 3, 50.0, carry_level=False)
+        finally:
+            eng.set_fused_select(prev)
+        got[fused] = (outs[0].cpu().numpy(), r)
+        _check_out(got[fused][0], r, ref, (case, "fused", fused, r["path"]))
+    SV.assert_same_bits(got[True][0], got[False][0], (case, "fused against unfused"))
+    _check_packed(eng, x, "haar", ref, (case,))
+
+
+# ---- absolute threshold ----
+
+ABS_CASES = ["zero_blocks", "subnormal", "huge", "nan_corner", "infs"]
+ABS_THR = 0.0125
+ABS_THR_SUBNORMAL = 0.0125 * 2.0 ** -126
+
+
+@pytest.mark.parametrize("shape,wavelet,level,path", [
+    ((4, 3, 7, 7), "db2", 3, TINY), ((4, 3, 7, 7), "bior3.3", 5, TINY),
+    ((6, 1, 8, 8), "db2", 3, TINY), ((6, 1, 8, 8), "bior3.3", 5, TINY),
+    ((3, 2, 9, 9), "db2", 3, CHAIN), ((3, 2, 9, 9), "bior3.3", 5, CHAIN),
+    (SHAPE, "db8", 3, CHAIN)])
+def test_absolute_threshold(eng, shape, wavelet, level, path):
+    """k_abs_tiny and the chain (tiled at the large shape, per-point at 9 x 9) at levels the
+    percentile path would clamp; nonzero_in / nonzero_out count a NaN as NumPy does, as nonzero."""
+    cs = inputs(shape)
+    for name in ABS_CASES:
+        thr = ABS_THR_SUBNORMAL if name == "subnormal" else ABS_THR
+        assert name != "subnormal" or 0 < np.float32(thr) < np.float32(2.0 ** -126)
+        x_np = cs[name]
+        with np.errstate(all="ignore"):
+            ref = abs_oracle(x_np, wavelet, level, thr)
+        x = _dev(x_np)
+        outs, (r,) = eng.prune_abs([x], wavelet, level, thr)
+        tag = (shape, wavelet, level, name)
+        out = outs[0].cpu().numpy()
+        SV.assert_same_bits(out, ref, tag)
+        assert SV.neg_zero_words(out) == 0 and SV.neg_zero_words(ref) == 0, tag
+        assert r["path"] == path and r["level"] == level and r["numel"] == x_np.size, (tag, r)
+        assert r["thr32_bits"] == G.f32_bits(thr), tag
+        assert r["nonzero_in"] == int(np.count_nonzero(x_np)), tag
+        assert r["nonzero_out"] == int(np.count_nonzero(ref)), tag
+        pr, pc = O.packed_shape(shape[-2], shape[-1], level)
+        assert r["coeff_numel"] == x_np.size // (shape[-2] * shape[-1]) * pr * pc, tag
+        if name in ("nan_corner", "infs"):
+            assert np.isnan(ref).any(), tag
+        # the packed array at the level as given (the component entry's chain, whichever kernel pruned)
+        with np.errstate(all="ignore"):
+            P_ref = O.wavedec2_packed(x_np, wavelet, level)
+        P = eng.wavedec2_packed(x, wavelet, level).cpu().numpy()
+        SV.assert_same_bits(P, P_ref, (tag, "packed"))
+        assert SV.neg_zero_words(P) == 0, tag
+
+
+# ---- extension modes ----
+
+with open(os.path.join(G.GOLDEN, "special_modes_manifest.json")) as _fh:
+    SM_MAN = json.load(_fh)
+SM_ARR = np.load(os.path.join(G.GOLDEN, "special_modes_cases.npz"))
+SM_SETTINGS = sorted({k.split("/")[0] for k in SM_MAN["cases"]})
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("setting", SM_SETTINGS)
+def test_extension_modes(eng, setting, mode):
+    """k_mtiny_fwd / k_mtiny_inv (7 x 7 images, haar level 2 and db2 level 1) and the per-level
+    kernels (db8 at 30 x 33, bior3.3 at 14 x 17) against the reference chain's fixture"""
+    assert SM_SETTINGS == ["level_bior33", "level_db8", "tiny_db2", "tiny_haar"]
+    keys = sorted(k for k, c in SM_MAN["cases"].items() if k.startswith(setting + "/") and c["mode"] == mode)
+    assert [SM_MAN["cases"][k]["case"] for k in keys] == ["infs", "nan_corner", "subnormal", "zero_blocks"]
+    for key in keys:
+        c = SM_MAN["cases"][key]
+        x_np = SV.cases(tuple(c["shape"]), SM_MAN["seed"], c["tid"])[c["case"]]
+        x = _dev(x_np)
+        outs, (r,) = eng.prune([x], c["wavelet"], c["level"], c["pct"], carry_level=False, mode=mode)
+        out = outs[0].cpu().numpy()
+        SV.assert_same_bits(out, SM_ARR[key + "/out"], (key, "out"))
+        assert SV.neg_zero_words(out) == 0, key
+        SV.assert_same_bits(np.float64(r["thr64"]), np.float64(float.fromhex(c["thr64_hex"])), (key, "thr64"))
+        SV.assert_same_bits(SV.f32_from_bits(r["thr32_bits"]), SV.f32_from_bits(c["thr32_bits"]), (key, "thr32"))
+        SV.assert_same_bits(SV.f32_from_bits(r["max_abs_bits"]), SV.f32_from_bits(c["max_abs_bits"]), (key, "max_abs"))
+        assert r["zero_count"] == c["zero_count"] and r["eff_level"] == c["eff_level"], (key, r)
+        assert r["coeff_numel"] == c["coeff_numel"] and r["numel"] == out.size, (key, r)
+        P = eng.wavedec2_packed_mode(x, c["wavelet"], c["eff_level"], mode).cpu().numpy()
+        assert list(P.shape) == c["packed_shape"], key
+        assert int(np.isnan(P).sum()) == c["packed_nan"] and int(np.isinf(P).sum()) == c["packed_inf"], key
+        assert SV.neg_zero_words(P) == 0, key
+        assert SV.bits_hash(P) == c["packed_hash"], (key, "packed")
+
+
+# ---- sweep ----
+
+@pytest.mark.parametrize("case", ["nan_interior", "infs"])
+def test_sweep_over_transformed_tensors(eng, case):
+    """one prune_sweep of three transformed tensors at percentiles 0, 50 and 100: the first holds
+    blocks of zeros, the third a NaN or the infinities; each percentile against the oracle"""
+    shapes = [(2, 3, 8, 8), (96, 100), SHAPE]
+    xs_np = [inputs(shapes[0], 1)["zero_blocks"], inputs(shapes[1], 2)["plain"], inputs(SHAPE)[case]]
+    pcts = [0.0, 50.0, 100.0]
+    xs = [_dev(x) for x in xs_np]
+    got, recs = eng.prune_sweep(xs, "haar", 2, pcts, carry_level=False)
+    assert len(got) == len(recs) == len(pcts)
+    for k, p in enumerate(pcts):
+        for t, x_np in enumerate(xs_np):
+            ref = _ref(x_np, "haar", 2, p)
+            assert ref[1]["eff_level"] == 2
+            assert recs[k][t]["path"] == eng.MODE_SWEEP
+            _check_out(got[k][t].cpu().numpy(), recs[k][t], ref, (case, p, t))
+    for t, (x, x_np) in enumerate(zip(xs, xs_np)):
+        _check_packed(eng, x, "haar", _ref(x_np, "haar", 2, 50.0), (case, t))
