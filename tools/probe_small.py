@@ -3,7 +3,7 @@
 Build the probe library on the CPU side first:  python tools/probe_small.py --build
 then on the GPU box:                           python tools/probe_small.py
 It loads tools/mb/libwtprune_probe.so (k_small compiled with -DWTP_SM_PROBE: workgroup b writes
-s_memrealtime at phase i to stamps[2 + 16 b + i]), checks the result against the oracle and
+s_memrealtime at phase i to stamps[2 + 32 b + i]), checks the result against the oracle and
 prints, per phase, the median over workgroups and runs of (stamp - launch start) in microseconds.
 """
 import os

@@ -17,14 +17,14 @@
  *      statistics of np.percentile come out of the same three passes (NumPy 1.x _lerp);
  *   I  the tile synthesises its owned output block from the coefficient windows of every level
  *      (thresholded as they are loaded: the np.where of :31), all in LDS, and counts its zeros.
- * Every output sample is summed in PyWavelets' exact order: the tap tables built per level list
- * each output's (tap, source) pairs in wt_dwt_core.h's order, so results are bit-identical to
+ * Every output sample is summed in PyWavelets' exact order (small_taps.h: the slot and the order
+ * of every tap, checked on the host against wt_dwt_core.h), so results are bit-identical to
  * the per-level kernels and the oracle.  A barrier whose wait times out poisons the segment's
  * counter (res_wait in resident.inc semantics): the whole segment stores nothing to `out` and
  * records WTP_PATH_FAULT, and the caller re-runs it in the multi-launch form.
  */
-#include "wtp_internal.h"
-#include "small_geom.h"
+#include "wtp_device.h"
+#include "small_taps.h"
 
 #include <atomic>
 
@@ -67,17 +67,6 @@ struct alignas(128) SmallState {
 };
 static_assert(SM_MAX_SEG * sizeof(SmallState) <= SEG_PER_LAUNCH * sizeof(SelState), "small state fits the region");
 
-__device__ __forceinline__ uint32_t sm_abs_key(float x) { return __float_as_uint(x) & 0x7FFFFFFFu; }
-template <class T>
-__device__ __forceinline__ void sm_stc(T* p, T v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <class T>
-__device__ __forceinline__ T sm_ldc(const T* p) {
-    return __hip_atomic_load(const_cast<T*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ uint64_t sm_ticks() { return __builtin_amdgcn_s_memrealtime(); }
-
 /* a segment barrier: every wave drains its stores, lane 0 arrives with a returning add (its
  * own arrival is then performed, and the last arriver needs no poll); sm_wait polls (sc1) from
  * that value, with the poison-on-timeout rule of k_resident's res_wait (all-or-nothing over
@@ -89,20 +78,20 @@ __device__ __forceinline__ uint32_t sm_arrive(uint32_t* ctr) {
 }
 __device__ __forceinline__ bool sm_wait(uint32_t* ctr, uint32_t v0, uint32_t want, uint64_t timeout, int* s_ok) {
     if (threadIdx.x == 0) {
-        const uint64_t t0 = sm_ticks();
+        const uint64_t t0 = wall_ticks();
         int ok = 0;
         uint32_t v = v0;
         while (true) {
             if (v & RES_POISON) break;
             if (v >= want) { ok = 1; break; }
-            if (sm_ticks() - t0 >= timeout) { /* >=: a zero bound poisons at the first incomplete look */
+            if (wall_ticks() - t0 >= timeout) { /* >=: a zero bound poisons at the first incomplete look */
                 const uint32_t w = atomicCAS(ctr, v, v | RES_POISON);
                 if (w == v) break;
                 v = w; /* it moved: look again */
                 continue;
             }
             __builtin_amdgcn_s_sleep(1);
-            v = sm_ldc(ctr);
+            v = ldc<true>(ctr);
         }
         *s_ok = ok;
     }
@@ -113,62 +102,11 @@ __device__ __forceinline__ bool sm_wait(uint32_t* ctr, uint32_t v0, uint32_t wan
 /* two lanes of packed FP32 (v_pk_mul_f32 / v_pk_add_f32): the same IEEE operations per lane */
 typedef float sf2 __attribute__((ext_vector_type(2)));
 
-/* e / n and e % n for e < 2^24 without an integer division (n uniform, inv = 1.0f / n) */
-__device__ __forceinline__ void sm_divmod(int e, int n, float inv, int* q, int* r) {
-    int d = (int)((float)e * inv);
-    int m = e - d * n;
-    if (m < 0) { --d; m += n; }
-    if (m >= n) { ++d; m -= n; }
-    *q = d;
-    *r = m;
-}
-__device__ __forceinline__ int sm_wrap(int a, int N) { return a < N ? a : a - N; } /* a < 2N */
-
-
-__device__ __forceinline__ int sm_r4(int x) { return (x + 3) & ~3; } /* LDS regions start 16-byte aligned */
-
-/* Cross-lane scan on DPP (row_shr inside rows of 16 lanes, row_bcast:15/31 across rows), as in
- * wtp_device.h: a few VALU cycles per step where a shuffle pays an LDS round trip.  Whole wave. */
-template <int CTRL, int ROWM = 0xf, int BANKM = 0xf>
-__device__ __forceinline__ uint32_t sm_dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROWM, BANKM, false);
-}
-__device__ __forceinline__ uint32_t sm_wave_scan(uint32_t v) { /* inclusive */
-    v += sm_dpp<0x111>(v);
-    v += sm_dpp<0x112>(v);
-    v += sm_dpp<0x114>(v);
-    v += sm_dpp<0x118>(v);
-    v += sm_dpp<0x142, 0xa>(v);
-    v += sm_dpp<0x143, 0xc>(v);
-    return v;
-}
-
-/* wave-wide min / max / or / sum on DPP (lanes without a source keep their own value), the
- * result read from lane 63; every lane of the wave must be active */
-template <int CTRL, int ROWM = 0xf, int BANKM = 0xf>
-__device__ __forceinline__ uint32_t sm_dppk(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROWM, BANKM, false);
-}
-template <class Op>
-__device__ __forceinline__ uint32_t sm_wave_red(uint32_t v, const Op& op) {
-    v = op(v, sm_dppk<0x111>(v));
-    v = op(v, sm_dppk<0x112>(v));
-    v = op(v, sm_dppk<0x114>(v));
-    v = op(v, sm_dppk<0x118>(v));
-    v = op(v, sm_dppk<0x142, 0xa>(v));
-    v = op(v, sm_dppk<0x143, 0xc>(v));
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint32_t sm_wave_min(uint32_t v) { return sm_wave_red(v, [](uint32_t a, uint32_t b) { return a < b ? a : b; }); }
-__device__ __forceinline__ uint32_t sm_wave_max(uint32_t v) { return sm_wave_red(v, [](uint32_t a, uint32_t b) { return a > b ? a : b; }); }
-__device__ __forceinline__ uint32_t sm_wave_or(uint32_t v) { return sm_wave_red(v, [](uint32_t a, uint32_t b) { return a | b; }); }
-__device__ __forceinline__ uint32_t sm_wave_sum(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)sm_wave_scan(v), 63); }
-
 /* block-wide exclusive scan of one u32 per thread (DPP inside the waves, one LDS exchange
  * across them); *tot the block total */
 __device__ __forceinline__ uint32_t sm_scan(uint32_t v, uint32_t* wtot, uint32_t* tot) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t incl = sm_wave_scan(v);
+    const uint32_t incl = wave_scan_u32(v);
     if (lane == 63) wtot[wv] = incl;
     __syncthreads();
     uint32_t before = 0, all = 0;
@@ -181,112 +119,6 @@ __device__ __forceinline__ uint32_t sm_scan(uint32_t v, uint32_t* wtot, uint32_t
     __syncthreads();
     *tot = all;
     return before + incl - v;
-}
-
-/* Taps of one output, summed in PyWavelets' order (wt_dwt_core.h).  The interior form -- taps
- * j = 0, 1, ... ascending at consecutive descending window slots -- is recognised by its first
- * slot (the fast path: samples read back to back, taps from LDS by constant index); anything else
- * (the periodic wrap at the image edges, the split order of wt_ana_point / wt_syn_pass) walks
- * the taps one by one: tap q is j(q) = q < c1 ? c1 - 1 - q : q. */
-
-__device__ __forceinline__ int sm_mod1(int a, int m) { /* a in [-m, 2m) */
-    a += a < 0 ? m : 0;
-    return a >= m ? a - m : a;
-}
-
-/* analysis output m of window W (line N) reading window Wp (line Np): when the samples of its
- * taps j sit at consecutive window slots s0 - j (always for an even line: the periodic wrap keeps
- * them contiguous; for an odd line only away from the repeated end), (s0 << 5) | c1, where c1 is
- * the count of taps wt_ana_point adds first in descending j (0 in the interior); else -1 */
-__device__ __forceinline__ int sm_ana_fast(SmIvl W, int N, SmIvl Wp, int Np, int F, int m) {
-    const int i = F / 2 + 2 * sm_wrap(W.s + m, N);
-    const int s0 = sm_mod1(i - Wp.s, Np);
-    const int c1 = min(max(i - Np + 1, 0), F);
-    return (s0 >= F - 1 && ((Np & 1) == 0 || (i < Np && i - F + 1 >= 0))) ? (s0 << 5) | c1 : -1;
-}
-/* the general form: tap q's window slot and tap index */
-struct SmAna {
-    int i, c1, Ne;
-};
-__device__ __forceinline__ SmAna sm_ana_at(SmIvl W, int N, int Np, int F, int m) {
-    SmAna a;
-    a.i = F / 2 + 2 * sm_wrap(W.s + m, N);
-    a.c1 = min(max(a.i - Np + 1, 0), F);
-    a.Ne = Np + (Np & 1);
-    return a;
-}
-__device__ __forceinline__ int sm_ana_tap(const SmAna& a, SmIvl Wp, int Np, int q, int* j) {
-    const int jj = q < a.c1 ? a.c1 - 1 - q : q;
-    int r = a.i - jj; /* in [-F, 2 Np): one period either way */
-    r += r < 0 ? a.Ne : 0;
-    r -= r >= a.Ne ? a.Ne : 0;
-    const int src = r < Np ? r : Np - 1;
-    *j = jj;
-    return sm_mod1(src - Wp.s, Np);
-}
-
-/* synthesis site of output n of 2N (wt_syn_locate in 32 bits) */
-struct SmSite {
-    int i, par, special;
-};
-__device__ __forceinline__ SmSite sm_site(int n, int N, int F) {
-    const int H = F / 2, start = F / 4;
-    SmSite s;
-    s.special = 0;
-    if ((H & 1) == 0) {
-        if (n == 2 * N - 1) { s.i = start - 1; s.par = 0; s.special = 1; }
-        else if (n == 0) { s.i = start - 1; s.par = 1; s.special = 1; }
-        else if (n & 1) { s.i = start + (n - 1) / 2; s.par = 0; }
-        else { s.i = start + (n - 2) / 2; s.par = 1; }
-    } else {
-        s.i = start + n / 2;
-        s.par = n & 1;
-    }
-    return s;
-}
-/* synthesis output m of window O (line No) reading window S (line N): the wrap is purely periodic,
- * so the sources of taps j sit at slots s0 - j whenever the window holds them:
- * (s0 << 6) | (parity << 5) | c1 (c1: the taps wt_syn_pass adds first in descending j), else -1 */
-__device__ __forceinline__ int sm_syn_fast(SmIvl O, int No, SmIvl S, int N, int F, int m) {
-    const int H = F / 2;
-    const SmSite s = sm_site(sm_wrap(O.s + m, No), N, F);
-    const int s0 = sm_mod1(s.i - S.s, N);
-    const int c1 = s.special ? min(max(s.i + 1, 0), H) : (s.i < N ? 0 : min(max(s.i - N + 1, 0), H));
-    return s0 >= H - 1 ? (s0 << 6) | (s.par << 5) | c1 : -1;
-}
-
-/* sum over T taps in PyWavelets' order: the c1 taps j = c1-1 .. 0 first, then j = c1 .. T-1;
- * v(j) the sample of tap j, c(j) its coefficient (compile-time j: registers, no indexing) */
-template <int T, class V, class C, class A>
-__device__ __forceinline__ void sm_order(int c1, bool plain, const V& v, const C& c, const A& acc) {
-    if (plain) {
-#pragma unroll
-        for (int j = 0; j < T; ++j) acc(c(j), v(j));
-    } else {
-#pragma unroll
-        for (int j = T - 1; j >= 0; --j)
-            if (j < c1) acc(c(j), v(j));
-#pragma unroll
-        for (int j = 0; j < T; ++j)
-            if (j >= c1) acc(c(j), v(j));
-    }
-}
-struct SmSyn {
-    int i, par, c1;
-};
-__device__ __forceinline__ SmSyn sm_syn_at(SmIvl O, int No, int N, int F, int m) {
-    const int H = F / 2;
-    const SmSite s = sm_site(sm_wrap(O.s + m, No), N, F);
-    SmSyn y;
-    y.i = s.i;
-    y.par = s.par;
-    y.c1 = s.special ? min(max(s.i + 1, 0), H) : (s.i < N ? 0 : min(max(s.i - N + 1, 0), H));
-    return y;
-}
-__device__ __forceinline__ int sm_syn_tap(const SmSyn& y, SmIvl S, int N, int q, int* ci) {
-    const int j = q < y.c1 ? y.c1 - 1 - q : q;
-    *ci = 2 * j + y.par;
-    return sm_mod1(sm_mod1(y.i - j, N) - S.s, N);
 }
 
 /* FT: the filter length as a compile-time constant (0: any, from the taps) -- the interior
@@ -308,7 +140,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
     __shared__ WinLvl s_wl[SM_LMAX + 2];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const uint32_t q = head->parity;
-    if (t.stamps && tid == 0) atomicMin(t.stamps, sm_ticks()); /* measurement only */
+    if (t.stamps && tid == 0) atomicMin(t.stamps, wall_ticks()); /* measurement only */
     {   /* clear this workgroup's slice of the idle region (the previous launch's) */
         uint4* idle = reinterpret_cast<uint4*>(sel_region(head, q ^ 1u));
         constexpr int NV4 = (int)(SEL_REGION / 16);
@@ -352,8 +184,8 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
             const int i = (tid - 128) / SM_F_MAX, j = (tid - 128) - i * SM_F_MAX;
             staps[i][j] = t.tp.f[i][j];
         } else if (tid == SM_THREADS - 1 && lt == 0) { /* memory-side words: later adds come from other workgroups */
-            sm_stc(reinterpret_cast<unsigned long long*>(&res[g.res].zero_count), 0ull);
-            sm_stc(&res[g.res].path, 0);
+            stc(reinterpret_cast<unsigned long long*>(&res[g.res].zero_count), 0ull);
+            stc(&res[g.res].path, 0);
         }
     }
     for (int i = tid; i < 4096; i += SM_THREADS) hist[i] = 0u;
@@ -510,10 +342,10 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
                 const int lr = r - axr.olo[k], lc = c - axc.olo[k];
                 if (lr >= 0 && lr < ohr && lc >= 0 && lc < ohc) {
                     const int offR = g.offR[k], offC = g.offC[k];
-                    sm_stc(P + (int64_t)r * g.PC + offC + c, ad);
-                    sm_stc(P + (int64_t)(offR + r) * g.PC + c, da);
-                    sm_stc(P + (int64_t)(offR + r) * g.PC + offC + c, dd);
-                    const uint32_t k1 = sm_abs_key(ad), k2 = sm_abs_key(da), k3 = sm_abs_key(dd);
+                    stc(P + (int64_t)r * g.PC + offC + c, ad);
+                    stc(P + (int64_t)(offR + r) * g.PC + c, da);
+                    stc(P + (int64_t)(offR + r) * g.PC + offC + c, dd);
+                    const uint32_t k1 = abs_key(ad), k2 = abs_key(da), k3 = abs_key(dd);
                     const int li = kbase + lr * ohc + lc;
                     K[li] = k1;
                     K[li + plane] = k2;
@@ -523,8 +355,8 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
                     atomicAdd(&hist[k3 >> 19], 1u);
                     mx = max(mx, max(k1, max(k2, k3)));
                     if (last) {
-                        sm_stc(P + (int64_t)r * g.PC + c, aa);
-                        const uint32_t k0 = sm_abs_key(aa);
+                        stc(P + (int64_t)r * g.PC + c, aa);
+                        const uint32_t k0 = abs_key(aa);
                         K[li + 3 * plane] = k0;
                         atomicAdd(&hist[k0 >> 19], 1u);
                         mx = max(mx, k0);
@@ -540,7 +372,9 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
     const uint32_t npad = lt == 0 ? (uint32_t)g.npad : 0u;
     if (tid == 0 && npad) hist[0] += npad;
     {
-        const uint32_t m = sm_wave_max(mx);
+        /* the keep-own-value form: wave_max_u32's zero-source steps cost k_small<18> two more
+         * spilled registers */
+        const uint32_t m = wave_red_u32(mx, [](uint32_t a, uint32_t b) { return a > b ? a : b; });
         if (lane == 0) wred[wv] = m;
     }
     __syncthreads();
@@ -563,7 +397,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
         const uint32_t nsh = (gridDim.x - sh + NSHARD - 1) / NSHARD; /* workgroups of this shard */
         const uint32_t nact = min((uint32_t)NSHARD, gridDim.x);     /* shards with workgroups */
         if (atomicAdd(&br->arrive[sh][0], 1u) == nsh - 1u && atomicAdd(&br->arrive[0][16], 1u) == nact - 1u)
-            sm_stc(&head->parity, q + 1u);
+            stc(&head->parity, q + 1u);
     }
     /* inverse arena: [owned keys | coefficient windows of levels 1..L | synthesised cA | row-pass
      * rows | tap tables]; level k's windows: cV (ad), cH (da), cD (dd) planes, and cA at level L */
@@ -634,7 +468,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
     if (ok) {
         /* digit 1: the 12-bit bin of ra */
         if (tid == 0) { s_fill = 0; s_min[0] = 0xFFFFFFFFu; s_min[1] = 0xFFFFFFFFu; }
-        locate([&](int i) { return sm_ldc(st->h1 + i); }, 4096, ra0, ra0);
+        locate([&](int i) { return ldc<true>(st->h1 + i); }, 4096, ra0, ra0);
         d1 = (uint32_t)s_dig[0];
         rem = ra0 - s_bef[0];
         SM_PROBE(2);
@@ -646,19 +480,19 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
             const uint32_t b12 = k >> 19;
             if (b12 == d1) {
                 const uint32_t p = atomicAdd(&s_fill, 1u);
-                if (p < (uint32_t)SM_SLOT_KEYS) sm_stc(slot + 3 + p, k);
+                if (p < (uint32_t)SM_SLOT_KEYS) stc(slot + 3 + p, k);
             } else if (b12 > d1) {
                 mn = min(mn, k);
             }
         }
-        mn = sm_wave_min(mn);
+        mn = wave_min_u32(mn);
         if (lane == 0 && mn != 0xFFFFFFFFu) atomicMin(&s_min[0], mn);
         __syncthreads();
         if (tid == 0) {
             const uint32_t f = s_fill;
-            sm_stc(slot, min(f, (uint32_t)SM_SLOT_KEYS) | (f > (uint32_t)SM_SLOT_KEYS ? 0x80000000u : 0u));
-            sm_stc(slot + 1, (npad && d1 == 0) ? npad : 0u);
-            sm_stc(slot + 2, s_min[0]);
+            stc(slot, min(f, (uint32_t)SM_SLOT_KEYS) | (f > (uint32_t)SM_SLOT_KEYS ? 0x80000000u : 0u));
+            stc(slot + 1, (npad && d1 == 0) ? npad : 0u);
+            stc(slot + 2, s_min[0]);
         }
         SM_PROBE(3);
         const uint32_t a1 = sm_arrive(&st->bar[1][0]);
@@ -669,7 +503,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
 #pragma unroll
         for (int u = 0; u < SM_PF; ++u) {
             const int e = tid + u * SM_THREADS;
-            pv[u] = e < nwin ? sm_ldc(P + woff[u]) : 0.0f;
+            pv[u] = e < nwin ? ldc<true>(P + woff[u]) : 0.0f;
         }
         ok = sm_wait(&st->bar[1][0], a1, nwg, tmo, &s_ok);
         SM_PROBE(5);
@@ -678,12 +512,12 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
             const int e = tid + u * SM_THREADS;
             if (e < nwin) WIN[e] = pv[u];
         }
-        for (int e = tid + SM_PF * SM_THREADS; e < nwin; e += SM_THREADS) WIN[e] = sm_ldc(win_src(e));
+        for (int e = tid + SM_PF * SM_THREADS; e < nwin; e += SM_THREADS) WIN[e] = ldc<true>(win_src(e));
         SM_PROBE(7);
     }
     if (ok) {
         /* every slot of the segment into LDS (and the segment's largest key, final since barrier 0) */
-        mk = sm_ldc(&st->maxkey);
+        mk = ldc<true>(&st->maxkey);
         const uint32_t* segs = t.slots + (int64_t)g.wg_begin * SM_SLOT_WORDS;
         const int nw = (int)nwg * SM_SLOT_WORDS;
         constexpr int GPT = SM_GATHER / SM_THREADS;
@@ -691,7 +525,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
 #pragma unroll
         for (int u = 0; u < GPT; ++u) {
             const int i = tid + u * SM_THREADS;
-            gv[u] = i < nw ? sm_ldc(segs + i) : 0u;
+            gv[u] = i < nw ? ldc<true>(segs + i) : 0u;
         }
 #pragma unroll
         for (int u = 0; u < GPT; ++u) {
@@ -713,9 +547,9 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
                 zz += G[w * SM_SLOT_WORDS + 1];
                 mw = min(mw, G[w * SM_SLOT_WORDS + 2]);
             }
-            const uint32_t o = sm_wave_or(oo), c = sm_wave_sum(cc);
-            zz = sm_wave_sum(zz);
-            mw = sm_wave_min(mw);
+            const uint32_t o = wave_or_u32(oo), c = wave_sum_u32(cc);
+            zz = wave_sum_u32(zz);
+            mw = wave_min_u32(mw);
             if (lane == 0) { s_hdr[0] = o; s_hdr[1] = c; s_hdr[2] = zz; s_hdr[3] = mw; }
         }
         /* a thread's keys: entries tid + u * SM_THREADS of the slot array, read while wave 0 reduces */
@@ -762,7 +596,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
                     if (kv[u] && a == da) s_list[atomicAdd(&s_lc, 1u)] = kk[u];
                     else if (kv[u] && a > da) mnA = min(mnA, kk[u]);
                 }
-                mnA = sm_wave_min(mnA);
+                mnA = wave_min_u32(mnA);
                 if (lane == 0 && mnA != 0xFFFFFFFFu) atomicMin(&s_min[1], mnA);
                 __syncthreads();
                 if (wv == 0) {
@@ -790,7 +624,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
                 if (kv[u] && a == da) atomicAdd(&hb[kk[u] & 511u], 1u);
                 else if (kv[u] && a > da) mnA = min(mnA, kk[u]);
             }
-            mnA = sm_wave_min(mnA);
+            mnA = wave_min_u32(mnA);
             if (lane == 0 && mnA != 0xFFFFFFFFu) atomicMin(&s_min[1], mnA);
             if (tid == 0 && z && da == 0) hb[0] += z;
             __syncthreads();
@@ -822,7 +656,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
         const uint32_t a2 = sm_arrive(&st->bar[2][0]);
         ok = sm_wait(&st->bar[2][0], a2, nwg, tmo, &s_ok);
         if (ok) {
-            locate([&](int i) { return sm_ldc(st->h2 + i); }, 2048, r, r);
+            locate([&](int i) { return ldc<true>(st->h2 + i); }, 2048, r, r);
             r -= s_bef[0];
             prefix = (prefix << 11) | (uint32_t)s_dig[0];
             for (int i = tid; i < 256; i += SM_THREADS) hist[i] = 0u;
@@ -834,7 +668,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
                 if ((k >> 8) == prefix) atomicAdd(&hist[k & 255u], 1u);
                 else if ((k >> 8) > prefix) mn = min(mn, k);
             }
-            mn = sm_wave_min(mn);
+            mn = wave_min_u32(mn);
             if (lane == 0 && mn != 0xFFFFFFFFu) atomicMin(&s_min[0], mn);
             if (tid == 0 && npad && prefix == 0) hist[0] += npad;
             __syncthreads();
@@ -846,16 +680,16 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
         }
         if (ok) {
             const int64_t rb = g.above ? r : r + 1;
-            locate([&](int i) { return sm_ldc(st->h3 + i); }, 256, r, rb);
+            locate([&](int i) { return ldc<true>(st->h3 + i); }, 256, r, rb);
             ka = (prefix << 8) | (uint32_t)s_dig[0];
-            kb = s_dig[1] >= 0 ? ((prefix << 8) | (uint32_t)s_dig[1]) : ~sm_ldc(&st->notmin);
+            kb = s_dig[1] >= 0 ? ((prefix << 8) | (uint32_t)s_dig[1]) : ~ldc<true>(&st->notmin);
         }
     }
     if (!ok) {
         if (tid == 0) atomicMax(&res[g.res].path, (int32_t)MODE_FAULT);
         return; /* nothing stored to `out`: the caller's input and output are untouched */
     }
-    if (ovf) mk = sm_ldc(&st->maxkey);
+    if (ovf) mk = ldc<true>(&st->maxkey);
     /* threshold: numpy/lib/function_base.py _lerp -- diff in float32, the blend in float64 */
     const float fa = __uint_as_float(ka), fb = __uint_as_float(kb);
     const float diff = fb - fa;
@@ -985,7 +819,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
         __syncthreads();
     }
     {
-        const uint32_t zz = sm_wave_sum((uint32_t)z);
+        const uint32_t zz = wave_sum_u32((uint32_t)z);
         if (lane == 0) wred[wv] = zz;
         __syncthreads();
         if (tid == 0) {
@@ -1007,7 +841,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
     if (t.stamps) { /* measurement only: the workgroup's end, once its stores have completed */
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (tid == 0) atomicMax(t.stamps + 1, sm_ticks());
+        if (tid == 0) atomicMax(t.stamps + 1, wall_ticks());
         SM_PROBE(15);
     }
 }
@@ -1023,9 +857,9 @@ int small_capacity() {
     }
     int cus = 0, cap = -1;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
-        const void* ks[] = {(const void*)k_small<0>, (const void*)k_small<2>, (const void*)k_small<4>,
-                            (const void*)k_small<6>, (const void*)k_small<8>, (const void*)k_small<10>,
-                            (const void*)k_small<12>, (const void*)k_small<16>, (const void*)k_small<18>};
+#define SM_INSTANCE(ft) (const void*)k_small<ft>,
+        const void* ks[] = {SM_SPECIALISED(SM_INSTANCE)(const void*) k_small<0>};
+#undef SM_INSTANCE
         cap = cus; /* one workgroup per CU, if every instance can hold one */
         for (const void* k : ks) {
             int per = 0;
@@ -1041,14 +875,10 @@ void launch_small(const SmallTable& t0, SelHeader* head, wtp_result* res, hipStr
     t.timeout = resident_timeout_us() * 100u; /* 100 MHz wall clock */
     t.stamps = kernel_stamps();
     switch (t.tp.F) {
-    case 2: hipLaunchKernelGGL(k_small<2>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
-    case 4: hipLaunchKernelGGL(k_small<4>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
-    case 6: hipLaunchKernelGGL(k_small<6>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
-    case 8: hipLaunchKernelGGL(k_small<8>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
-    case 10: hipLaunchKernelGGL(k_small<10>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
-    case 12: hipLaunchKernelGGL(k_small<12>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
-    case 16: hipLaunchKernelGGL(k_small<16>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
-    case 18: hipLaunchKernelGGL(k_small<18>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
+#define SM_LAUNCH(ft) \
+    case ft: hipLaunchKernelGGL(k_small<ft>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
+        SM_SPECIALISED(SM_LAUNCH)
+#undef SM_LAUNCH
     default: hipLaunchKernelGGL(k_small<0>, dim3(t.nblk), dim3(SM_THREADS), 0, s, t, head, res); break;
     }
 }

@@ -70,16 +70,31 @@ WT_SM SmIvl sm_fwd_taps(SmIvl W, int32_t N, int32_t Np, int32_t F) {
                     sm_ext_image(1 - F / 2, 2 * (l2 - 1) + F - 1, Np), Np);
 }
 
-/* synthesis site of output n of 2N (wt_syn_locate), as the unwrapped source position iu: the
- * H-even special last output n = 2N - 1 reads i - j + N */
-WT_SM int32_t sm_iu(int32_t n, int32_t N, int32_t F) {
-    const int32_t H = F / 2, start = F / 4, M = 2 * N;
+/* synthesis site of output n of 2N (wt_syn_locate in 32 bits): the one statement of it, for the
+ * planner's windows (sm_iu) and the kernel's walk (small_taps.h) */
+struct SmSite {
+    int32_t i, par, special;
+};
+WT_SM SmSite sm_site(int32_t n, int32_t N, int32_t F) {
+    const int32_t H = F / 2, start = F / 4;
+    SmSite s;
+    s.special = 0;
     if ((H & 1) == 0) {
-        if (n == M - 1) return start - 1 + N;
-        if (n == 0) return start - 1;
-        return (n & 1) ? start + (n - 1) / 2 : start + (n - 2) / 2;
+        if (n == 2 * N - 1) { s.i = start - 1; s.par = 0; s.special = 1; }
+        else if (n == 0) { s.i = start - 1; s.par = 1; s.special = 1; }
+        else if (n & 1) { s.i = start + (n - 1) / 2; s.par = 0; }
+        else { s.i = start + (n - 2) / 2; s.par = 1; }
+    } else {
+        s.i = start + n / 2;
+        s.par = n & 1;
     }
-    return start + n / 2;
+    return s;
+}
+/* the site as the unwrapped source position iu: the H-even special last output n = 2N - 1
+ * reads i - j + N */
+WT_SM int32_t sm_iu(int32_t n, int32_t N, int32_t F) {
+    const SmSite s = sm_site(n, N, F);
+    return (s.special && n == 2 * N - 1) ? s.i + N : s.i;
 }
 
 /* synthesis: the level-k coefficients (line length N) read by the outputs O (line length No) */
@@ -111,8 +126,10 @@ struct SmAxis {
 
 #if defined(__HIPCC__)
 #define SM_NOUNROLL _Pragma("unroll 1")
+#define SM_UNROLL _Pragma("unroll")
 #else
 #define SM_NOUNROLL
+#define SM_UNROLL
 #endif
 WT_SM void sm_axis_fwd(int32_t t, int32_t T, int32_t L, const int32_t* N, int32_t F, SmAxis* a) {
     SM_NOUNROLL

@@ -85,6 +85,25 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+/* wave-wide reduction where a lane without a DPP source keeps its own value (old = v): min needs
+ * it, the zero a dpp_u32 step reads there would win.  The result is read from lane 63. */
+template <int CTRL, int ROWM = 0xf, int BANKM = 0xf>
+__device__ __forceinline__ uint32_t dpp_keep_u32(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROWM, BANKM, false);
+}
+template <class Op>
+__device__ __forceinline__ uint32_t wave_red_u32(uint32_t v, const Op& op) {
+    v = op(v, dpp_keep_u32<0x111>(v));
+    v = op(v, dpp_keep_u32<0x112>(v));
+    v = op(v, dpp_keep_u32<0x114>(v));
+    v = op(v, dpp_keep_u32<0x118>(v));
+    v = op(v, dpp_keep_u32<0x142, 0xa>(v));
+    v = op(v, dpp_keep_u32<0x143, 0xc>(v));
+    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_red_u32(v, [](uint32_t a, uint32_t b) { return a < b ? a : b; }); }
+__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) { return wave_red_u32(v, [](uint32_t a, uint32_t b) { return a | b; }); }
+
 /* exact 64-bit sum (three 32-bit reductions of 16/16/32-bit fields) */
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
     const uint32_t lo = wave_sum_u32((uint32_t)v & 0xFFFFu);
