@@ -22,7 +22,7 @@ MODES = ["zero", "constant", "symmetric", "reflect", "periodic"]
 def build(name="modescore", flags=("-O2",)):
     os.makedirs(BUILD, exist_ok=True)
     exe = os.path.join(BUILD, name)
-    deps = [SRC, os.path.join(CSRC, "wt_modes_core.h"), os.path.join(CSRC, "wt_dwt_core.h")]
+    deps = [SRC] + [os.path.join(CSRC, h) for h in ("wt_modes_core.h", "wt_tiny_arena.h", "wt_dwt_core.h")]
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off"] + list(flags) + ["-o", exe, SRC])
     return exe

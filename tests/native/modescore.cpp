@@ -8,8 +8,16 @@
 //   2 mode F H W L                                 -> R[0..L] C[0..L] PR PC outH outW
 //   3 mode F B H W L thr | taps[4F] | x[B H W]     -> PR PC | packed[B PR PC] | out[B H W]
 //   4 H W L F                                      -> wtm_tiny_lanes_log2 (-1: not a tiny tensor)
+//   5 mode F B H W L NL thr | taps[4F] | x[B H W]  -> as record 3
+//   6 mode F H W L                                 -> wtm_levels_ok | R[0..L] C[0..L] offR[1..L] offC[1..L] PR PC
+//                                                     of wtm_tiny_geometry | the same of wtm_geom
 // Record 3 is wavedec2 + coeffs_to_array, np.where(|c| < thr, 0, c), waverec2 and the crop to
-// H x W, level by level as the kernels of csrc/modes.hip run them.
+// H x W, level by level as the per-level kernels of csrc/modes.hip run them.  Record 5 is the same
+// transform of a tiny tensor as k_mtiny_fwd / k_mtiny_inv run it: wtm_tiny_fwd / wtm_tiny_inv on
+// images in groups of NL at lane offsets of one arena of exactly the words the area functions
+// report (so a word outside them is a heap overflow under AddressSanitizer), sentinels in it
+// before each kernel's part, D zero-filled before the forward and thresholded on load.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -75,8 +83,6 @@ static bool rec_geom() {
     return true;
 }
 
-static float mask(float c, float thr) { return (fabsf(c) < thr) ? 0.0f : c; }
-
 static bool rec_image() {
     if (!have(7)) return false;
     const int mode = rd_i(), F = rd_i(), B = rd_i(), H = rd_i(), W = rd_i(), L = rd_i();
@@ -119,11 +125,11 @@ static bool rec_image() {
                 for (int64_t n = 0; n < oW; ++n) {
                     lo[(size_t)(r * oW + n)] = wtm_syn_point(
                         n, F, &taps[2 * F], &taps[3 * F],
-                        [&](int64_t q) { return k == L ? mask(Pb[r * PC + q], thr) : a.at((size_t)(r * C + q)); },
-                        [&](int64_t q) { return mask(Pb[r * PC + g.offC[k] + q], thr); });
+                        [&](int64_t q) { return k == L ? wt_thr_mask(Pb[r * PC + q], thr) : a.at((size_t)(r * C + q)); },
+                        [&](int64_t q) { return wt_thr_mask(Pb[r * PC + g.offC[k] + q], thr); });
                     hi[(size_t)(r * oW + n)] = wtm_syn_point(
-                        n, F, &taps[2 * F], &taps[3 * F], [&](int64_t q) { return mask(Pb[(g.offR[k] + r) * PC + q], thr); },
-                        [&](int64_t q) { return mask(Pb[(g.offR[k] + r) * PC + g.offC[k] + q], thr); });
+                        n, F, &taps[2 * F], &taps[3 * F], [&](int64_t q) { return wt_thr_mask(Pb[(g.offR[k] + r) * PC + q], thr); },
+                        [&](int64_t q) { return wt_thr_mask(Pb[(g.offR[k] + r) * PC + g.offC[k] + q], thr); });
                 }
             for (int64_t m = 0; m < oH; ++m)
                 for (int64_t n = 0; n < oW; ++n)
@@ -138,6 +144,70 @@ static bool rec_image() {
     wr_i((int32_t)PC);
     wr_fv(P);
     wr_fv(out);
+    return true;
+}
+
+static bool rec_tiny() {
+    if (!have(8)) return false;
+    const int mode = rd_i(), F = rd_i(), B = rd_i(), H = rd_i(), W = rd_i(), L = rd_i(), NL = rd_i();
+    const float thr = rd_f();
+    if (B < 1 || NL < 1 || NL > 64 || wtm_tiny_lanes_log2(H, W, L, F) < 0 || !wtm_levels_ok(H, W, L, F, mode)) return false;
+    if (!have((size_t)4 * F + (size_t)B * H * W)) return false;
+    const std::vector<float> taps = rd_fv((size_t)4 * F), x = rd_fv((size_t)B * H * W);
+    wtm_tiny_geom g;
+    wtm_tiny_geometry(H, W, L, F, g);
+    const int HW = H * W, PP = g.PR * g.PC;
+    const int aw = wtm_tiny_area_a(H, W, L, F), tw = wtm_tiny_area_t(H, W, L, F), dw = wtm_tiny_area_d(H, W, L, F);
+    if (dw != PP) return false;
+    std::vector<float> arena((size_t)(aw + tw + dw) * NL), P((size_t)B * PP), out((size_t)B * HW);
+    float *A = arena.data(), *T = A + (size_t)aw * NL, *D = T + (size_t)tw * NL;
+    for (int b0 = 0; b0 < B; b0 += NL) {
+        const int n = B - b0 < NL ? B - b0 : NL;
+        /* k_mtiny_fwd */
+        std::fill(arena.begin(), arena.end(), -77.0f);
+        for (int i = 0; i < n; ++i)
+            for (int s = 0; s < HW; ++s) A[(size_t)s * NL + i] = x[(size_t)(b0 + i) * HW + s];
+        for (int i = 0; i < NL; ++i)
+            for (int s = 0; s < PP; ++s) D[(size_t)s * NL + i] = 0.0f;
+        for (int i = 0; i < n; ++i) wtm_tiny_fwd(A + i, T + i, D + i, NL, g, L, F, mode, &taps[0], &taps[F]);
+        for (int i = 0; i < n; ++i)
+            for (int s = 0; s < PP; ++s) P[(size_t)(b0 + i) * PP + s] = D[(size_t)s * NL + i];
+        /* k_mtiny_inv */
+        std::fill(arena.begin(), arena.end(), -77.0f);
+        for (int i = 0; i < n; ++i)
+            for (int s = 0; s < PP; ++s) D[(size_t)s * NL + i] = wt_thr_mask(P[(size_t)(b0 + i) * PP + s], thr);
+        for (int i = 0; i < n; ++i) wtm_tiny_inv(A + i, T + i, D + i, NL, g, L, F, &taps[2 * F], &taps[3 * F]);
+        for (int i = 0; i < n; ++i)
+            for (int s = 0; s < HW; ++s) out[(size_t)(b0 + i) * HW + s] = A[(size_t)s * NL + i];
+    }
+    wr_i(g.PR);
+    wr_i(g.PC);
+    wr_fv(P);
+    wr_fv(out);
+    return true;
+}
+
+static bool rec_tiny_geom() {
+    if (!have(5)) return false;
+    const int mode = rd_i(), F = rd_i(), H = rd_i(), W = rd_i(), L = rd_i();
+    if (L < 1 || L > WTM_TINY_LMAX || mode == WTM_PERIODIZATION) return false;
+    wtm_tiny_geom t;
+    wtm_tiny_geometry(H, W, L, F, t);
+    wt_level_geom g;
+    wtm_geom(H, W, L, F, mode, &g);
+    wr_i(wtm_levels_ok(H, W, L, F, mode));
+    for (int k = 0; k <= L; ++k) wr_i(t.R[k]);
+    for (int k = 0; k <= L; ++k) wr_i(t.C[k]);
+    for (int k = 1; k <= L; ++k) wr_i(t.offR[k]);
+    for (int k = 1; k <= L; ++k) wr_i(t.offC[k]);
+    wr_i(t.PR);
+    wr_i(t.PC);
+    for (int k = 0; k <= L; ++k) wr_i((int32_t)g.R[k]);
+    for (int k = 0; k <= L; ++k) wr_i((int32_t)g.C[k]);
+    for (int k = 1; k <= L; ++k) wr_i((int32_t)g.offR[k]);
+    for (int k = 1; k <= L; ++k) wr_i((int32_t)g.offC[k]);
+    wr_i((int32_t)g.PR);
+    wr_i((int32_t)g.PC);
     return true;
 }
 
@@ -164,7 +234,13 @@ int main(int argc, char** argv) {
     int n = 0;
     while (g_pos < g_in.size()) {
         const int kind = rd_i();
-        const bool ok = kind == 1 ? rec_line() : kind == 2 ? rec_geom() : kind == 3 ? rec_image() : kind == 4 ? rec_lanes() : false;
+        const bool ok = kind == 1   ? rec_line()
+                        : kind == 2 ? rec_geom()
+                        : kind == 3 ? rec_image()
+                        : kind == 4 ? rec_lanes()
+                        : kind == 5 ? rec_tiny()
+                        : kind == 6 ? rec_tiny_geom()
+                                    : false;
         if (!ok) {
             fprintf(stderr, "modescore: bad record %d (kind %d)\n", n, kind);
             fclose(g_out);

@@ -30,7 +30,7 @@ __device__ __forceinline__ unsigned abs_wave_sum(unsigned v) {
     return v;
 }
 
-__global__ __launch_bounds__(ABS_THREADS) void k_abs_tiny(AbsTable t, wtp_abs_result* __restrict__ res) {
+__global__ __launch_bounds__(TINY_THREADS) void k_abs_tiny(AbsTable t, wtp_abs_result* __restrict__ res) {
     __shared__ float lds[ABS_WAVE_WORDS];
     /* the four filters beside the arena: a tap is a broadcast LDS read that returns in order with
      * the sample reads, so an unrolled tap loop keeps several reads in flight (a scalar load per
@@ -57,13 +57,13 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_tiny(AbsTable t, wtp_abs_re
     float* D = T + abs_area_t(H, W, L) * NL;
 
     const int FP = ABS_TAP_WORDS / 4;
-    for (int e = threadIdx.x; e < 4 * F; e += ABS_THREADS) {
+    for (int e = threadIdx.x; e < 4 * F; e += TINY_THREADS) {
         const int k = e / F, j = e - k * F;
         ltap[k * FP + j] = t.tp.f[k][j];
     }
     /* coalesced read of the wave's images into the sample-major layout */
     unsigned z_in = 0, z_out = 0;
-    for (int e = lane; e < total; e += ABS_THREADS) {
+    for (int e = lane; e < total; e += TINY_THREADS) {
         const float v = in[e];
         const int img = e / HW, s = e - img * HW;
         A[s * NL + img] = v;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(ABS_THREADS) void k_abs_tiny(AbsTable t, wtp_abs_re
         abs_image(A + lane, T + lane, D + lane, NL, H, W, L, F, ltap, ltap + FP, ltap + 2 * FP, ltap + 3 * FP, thr);
     __syncthreads();
 
-    for (int e = lane; e < total; e += ABS_THREADS) {
+    for (int e = lane; e < total; e += TINY_THREADS) {
         const int img = e / HW, s = e - img * HW;
         const float v = A[s * NL + img];
         out[e] = v;
@@ -175,7 +175,7 @@ void launch_abs_zero(float* p, int64_t n, hipStream_t s) {
 }
 
 void launch_abs_tiny(const AbsTable& t, wtp_abs_result* res, hipStream_t s) {
-    hipLaunchKernelGGL(k_abs_tiny, dim3((unsigned)t.nwave), dim3(ABS_THREADS), 0, s, t, res);
+    hipLaunchKernelGGL(k_abs_tiny, dim3((unsigned)t.nwave), dim3(TINY_THREADS), 0, s, t, res);
 }
 
 void launch_abs_count(const float* x, int64_t n, unsigned long long* dst, wtp_abs_result* rec,

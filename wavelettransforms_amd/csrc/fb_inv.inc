@@ -79,7 +79,7 @@ __global__ __launch_bounds__(FB_THREADS) WTP_FB_INV_WPE void k_inv_level(InvGrou
      * across a barrier and write them over Aq/Dq (half the LDS per workgroup) */
     float2* LoHi = FT > 0 ? Aq : Dq + NRr * NCc;
     const float thr = a.thr ? *a.thr : 0.0f;      /* |c| < 0 never holds: no threshold  */
-    auto tl = [&](float c) { return (fabsf(c) < thr) ? 0.0f : c; };
+    auto tl = [&](float c) { return wt_thr_mask(c, thr); };
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const float* Pb = a.P + (int64_t)b * a.P_bs;
     const float* ab = a.a + (int64_t)b * a.a_bs;
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(FB_THREADS) WTP_FB_INT_WPE void k_inv_int(InvGroup 
     float2* LoHi = Aq;                           /* NR x IC, written over Aq/Dq after the row pass */
     const float* thrp = a.thr ? a.thr + thr_off_of(g.tz_off[item]) : nullptr;
     const float thr = thrp ? *thrp : 0.0f; /* |c| < 0 never holds: no threshold */
-    auto tl = [&](float c) { return (fabsf(c) < thr) ? 0.0f : c; };
+    auto tl = [&](float c) { return wt_thr_mask(c, thr); };
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     WTP_FPROBE(0);
     /* 1. the four coefficient tiles, thresholded on load: element e of the NR x NC window at

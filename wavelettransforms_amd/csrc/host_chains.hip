@@ -21,25 +21,16 @@ static void launch_tiny_chains(const std::vector<Chain>& cs, const Taps& tp, hip
     for (const Chain& c : cs) {
         const TPlan& p = *c.p;
         if (p.tiny_lg < 0) continue;
-        MTinySeg& sg = tab.s[tab.nseg];
-        sg.in = c.in;
-        sg.out = c.out;
+        MTinySeg& sg = tiny_append(tab, c.in, c.out, p.B, p.H, p.W, p.L, p.tiny_lg);
         sg.P = c.P;
         sg.thr = c.thr;
         sg.zc = c.zc;
-        sg.B = (int32_t)p.B;
-        sg.H = (uint8_t)p.H;
-        sg.W = (uint8_t)p.W;
-        sg.L = (uint8_t)p.L;
-        sg.nl_log2 = (uint8_t)p.tiny_lg;
         tab.mode = p.mode;
-        tab.wave_begin[tab.nseg++] = tab.nwave;
-        tab.nwave += (int32_t)((p.B + (1 << p.tiny_lg) - 1) >> p.tiny_lg);
     }
     if (!tab.nseg) return;
     tab.F = tp.F;
     for (int k = 0; k < 4; ++k)
-        for (int j = 0; j < tp.F && j < MT_F_MAX; ++j) tab.f[k][j] = tp.f[k][j];
+        for (int j = 0; j < tp.F && j < WTM_TINY_F_MAX; ++j) tab.f[k][j] = tp.f[k][j];
     if (inverse) launch_mtiny_inv(tab, s);
     else launch_mtiny_fwd(tab, s);
 }

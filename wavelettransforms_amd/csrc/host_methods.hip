@@ -106,24 +106,14 @@ static void abs_tiny_launches(const wtp_tensor* tensors, int ntensors, const Abs
     for (int t = 0; t <= ntensors; ++t) {
         const bool flush = t == ntensors || (tab.nseg == ABS_MAX_SEG) ||
                            (t < ntensors && a.path[t] == WTP_ABS_PATH_TINY &&
-                            (int64_t)tab.nwave + ((a.ps[t].B + (1 << a.nl_log2[t]) - 1) >> a.nl_log2[t]) > (int64_t)INT32_MAX);
+                            (int64_t)tab.nwave + tiny_waves(a.ps[t].B, a.nl_log2[t]) > (int64_t)INT32_MAX);
         if (flush && tab.nseg) {
             launch_abs_tiny(tab, results, s);
             reset();
         }
         if (t == ntensors || a.path[t] != WTP_ABS_PATH_TINY) continue;
         const TPlan& p = a.ps[t];
-        AbsSeg& sg = tab.s[tab.nseg];
-        sg.in = tensors[t].in;
-        sg.out = tensors[t].out;
-        sg.B = (int32_t)p.B;
-        sg.H = (uint8_t)p.H;
-        sg.W = (uint8_t)p.W;
-        sg.L = (uint8_t)p.L;
-        sg.nl_log2 = (uint8_t)a.nl_log2[t];
-        sg.res = t;
-        tab.wave_begin[tab.nseg++] = tab.nwave;
-        tab.nwave += (int32_t)((p.B + (1 << a.nl_log2[t]) - 1) >> a.nl_log2[t]);
+        tiny_append(tab, tensors[t].in, tensors[t].out, p.B, p.H, p.W, p.L, a.nl_log2[t]).res = t;
     }
 }
 

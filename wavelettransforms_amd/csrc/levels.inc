@@ -16,8 +16,6 @@ namespace wtp {
 /* ------------------------------------------------------------ filter bank --- */
 constexpr int DWT_THREADS = 256;
 
-__device__ __forceinline__ float thr_load(float c, float thr) { return (fabsf(c) < thr) ? 0.0f : c; }
-
 /* axis -2 analysis: in (B,R,C) -> L,H (B,Ro,C);  pywt dwtn first axis (_multidim.py:183-191) */
 __global__ __launch_bounds__(DWT_THREADS) void k_dwt_cols(const float* __restrict__ in, int64_t B, int64_t R,
                                                           int64_t C, Taps tp, float* __restrict__ L,
@@ -79,13 +77,13 @@ __global__ __launch_bounds__(DWT_THREADS) void k_idwt_rows(const float* __restri
         const float* rhi = tp.f[3];
         float vlo, vhi;
         if (a_from_P)
-            vlo = wt_syn_point(n, C, tp.F, rlo, rhi, [&](int64_t k) { return thr_load(arow[k], thr); },
-                               [&](int64_t k) { return thr_load(adr[k], thr); });
+            vlo = wt_syn_point(n, C, tp.F, rlo, rhi, [&](int64_t k) { return wt_thr_mask(arow[k], thr); },
+                               [&](int64_t k) { return wt_thr_mask(adr[k], thr); });
         else
             vlo = wt_syn_point(n, C, tp.F, rlo, rhi, [&](int64_t k) { return arow[k]; },
-                               [&](int64_t k) { return thr_load(adr[k], thr); });
-        vhi = wt_syn_point(n, C, tp.F, rlo, rhi, [&](int64_t k) { return thr_load(dar[k], thr); },
-                           [&](int64_t k) { return thr_load(ddr[k], thr); });
+                               [&](int64_t k) { return wt_thr_mask(adr[k], thr); });
+        vhi = wt_syn_point(n, C, tp.F, rlo, rhi, [&](int64_t k) { return wt_thr_mask(dar[k], thr); },
+                           [&](int64_t k) { return wt_thr_mask(ddr[k], thr); });
         lo[idx] = vlo;
         hi[idx] = vhi;
     }
@@ -142,8 +140,8 @@ __global__ __launch_bounds__(DWT_THREADS) void k_idwt1_level(const float* __rest
     unsigned long long z = 0;
     for (int64_t n = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; n < outN; n += (int64_t)gridDim.x * DWT_THREADS) {
         const float v = wt_syn_point(n, N, tp.F, tp.f[2], tp.f[3],
-                                     [&](int64_t k) { return ta ? thr_load(a[k], t) : a[k]; },
-                                     [&](int64_t k) { return td ? thr_load(d[k], t) : d[k]; });
+                                     [&](int64_t k) { return ta ? wt_thr_mask(a[k], t) : a[k]; },
+                                     [&](int64_t k) { return td ? wt_thr_mask(d[k], t) : d[k]; });
         y[n] = v;
         z += (v == 0.0f);
     }
@@ -159,7 +157,7 @@ __global__ __launch_bounds__(DWT_THREADS) void k_copy_threshold(const float* __r
     const float thr = thrp ? *thrp : 0.0f;
     unsigned long long z = 0;
     for (int64_t i = (int64_t)blockIdx.x * DWT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * DWT_THREADS) {
-        const float v = thr_load(P[i], thr);
+        const float v = wt_thr_mask(P[i], thr);
         out[i] = v;
         z += (v == 0.0f);
     }

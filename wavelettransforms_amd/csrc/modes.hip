@@ -4,10 +4,11 @@
  * arithmetic and the geometry are csrc/wt_modes_core.h, shared with the host-side check).
  *
  *   k_mtiny_fwd / k_mtiny_inv   tensors whose images are at most 8 x 8 (conv kernels): a wave per
- *                tensor slice, one image per lane in a sample-major LDS arena (k_abs_tiny's
- *                layout).  k_mtiny_fwd reads an image once, runs every analysis level on chip and
- *                stores the packed coefficient image, padding zeros included (the percentile's
- *                population); after the selection k_mtiny_inv reads the packed image once,
+ *                tensor slice, one image per lane in a sample-major LDS arena (wt_tiny_arena.h;
+ *                the level loops are wtm_tiny_fwd / wtm_tiny_inv of wt_modes_core.h).  k_mtiny_fwd
+ *                reads an image once, runs every analysis level on chip and stores the packed
+ *                coefficient image, padding zeros included (the percentile's population);
+ *                after the selection k_mtiny_inv reads the packed image once,
  *                thresholds it on load, runs every synthesis level and waverec2's crops on chip
  *                and stores the weights, counting their zeros.
  *   k_mdwt_cols / k_mdwt_rows / k_midwt_rows / k_midwt_cols   every other tensor, a level at a
@@ -27,8 +28,6 @@
 namespace wtp {
 
 constexpr int MDWT_THREADS = 256;
-
-__device__ __forceinline__ float mthr_load(float c, float thr) { return (fabsf(c) < thr) ? 0.0f : c; }
 
 /* axis -2 analysis: in (B, R, C) -> L, H (B, Ro, C), Ro = wtm_dec_len(R) */
 __global__ __launch_bounds__(MDWT_THREADS) void k_mdwt_cols(const float* __restrict__ in, int64_t B, int64_t R,
@@ -91,13 +90,13 @@ __global__ __launch_bounds__(MDWT_THREADS) void k_midwt_rows(const float* __rest
         const float* ddr = Pb + (offR + r) * PC + offC;
         float vlo;
         if (a_from_P)
-            vlo = wtm_syn_point(n, tp.F, tp.f[2], tp.f[3], [&](int64_t k) { return mthr_load(arow[k], thr); },
-                                [&](int64_t k) { return mthr_load(adr[k], thr); });
+            vlo = wtm_syn_point(n, tp.F, tp.f[2], tp.f[3], [&](int64_t k) { return wt_thr_mask(arow[k], thr); },
+                                [&](int64_t k) { return wt_thr_mask(adr[k], thr); });
         else
             vlo = wtm_syn_point(n, tp.F, tp.f[2], tp.f[3], [&](int64_t k) { return arow[k]; },
-                                [&](int64_t k) { return mthr_load(adr[k], thr); });
-        const float vhi = wtm_syn_point(n, tp.F, tp.f[2], tp.f[3], [&](int64_t k) { return mthr_load(dar[k], thr); },
-                                        [&](int64_t k) { return mthr_load(ddr[k], thr); });
+                                [&](int64_t k) { return wt_thr_mask(adr[k], thr); });
+        const float vhi = wtm_syn_point(n, tp.F, tp.f[2], tp.f[3], [&](int64_t k) { return wt_thr_mask(dar[k], thr); },
+                                        [&](int64_t k) { return wt_thr_mask(ddr[k], thr); });
         lo[idx] = vlo;
         hi[idx] = vhi;
     }
@@ -128,154 +127,54 @@ __global__ __launch_bounds__(MDWT_THREADS) void k_midwt_cols(const float* __rest
 }
 
 /* ------------------------------------------------------------- tiny images --- */
-/* The areas of a lane's image in the arena (wtm_tiny_areas): A the image / a level's
- * approximation / a level's synthesis output, T a level's two half transforms, D the packed
- * coefficient image (PR x PC, row pitch PC).  The geometry is wave-uniform, so every index below
- * is scalar arithmetic and every LDS access a uniform offset plus the lane. */
-struct MTinyGeom {
-    int R[MT_LMAX + 1], C[MT_LMAX + 1], offR[MT_LMAX + 1], offC[MT_LMAX + 1], PR, PC;
-};
-__device__ __forceinline__ void mtiny_geom(int H, int W, int L, int F, MTinyGeom& g) {
-    g.R[0] = H;
-    g.C[0] = W;
-    for (int k = 1; k <= L; ++k) { g.R[k] = (g.R[k - 1] + F - 1) >> 1; g.C[k] = (g.C[k - 1] + F - 1) >> 1; }
-    int aR = g.R[L], aC = g.C[L];
-    for (int k = L; k >= 1; --k) { g.offR[k] = aR; g.offC[k] = aC; aR += g.R[k]; aC += g.C[k]; }
-    g.PR = aR;
-    g.PC = aC;
-}
-
-__device__ __forceinline__ void mtiny_setup(const MTinyTable& t, float* ltap, int& sg, int& w) {
-    const int gw = blockIdx.x;
-    sg = 0;
-    for (int i = 1; i < t.nseg; ++i) sg += gw >= t.wave_begin[i];
-    w = gw - t.wave_begin[sg];
-    if (threadIdx.x < 4 * MT_F_MAX) ltap[threadIdx.x] = t.f[threadIdx.x / MT_F_MAX][threadIdx.x % MT_F_MAX];
-}
-
-__global__ __launch_bounds__(MT_THREADS) void k_mtiny_fwd(MTinyTable t) {
-    __shared__ float lds[MT_WAVE_WORDS];
-    __shared__ float ltap[4 * MT_F_MAX];
-    int sg, w;
-    mtiny_setup(t, ltap, sg, w);
-    const MTinySeg& S = t.s[sg];
+/* A wave's arena (wt_tiny_arena.h) holds the areas A, T and D of its images (wt_modes_core.h,
+ * where the per-image routines wtm_tiny_fwd / wtm_tiny_inv are).  The geometry is wave-uniform:
+ * thread 0 puts it into LDS (the level loops index it; private arrays would go to scratch). */
+__global__ __launch_bounds__(TINY_THREADS) void k_mtiny_fwd(MTinyTable t) {
+    __shared__ float lds[WTM_WAVE_WORDS];
+    __shared__ float ltap[4 * WTM_TINY_F_MAX];
+    const TinyWave v = tiny_wave(t);
+    tiny_stage_taps(ltap, WTM_TINY_F_MAX, WTM_TINY_F_MAX, [&](int k, int j) { return t.f[k][j]; });
+    const MTinySeg& S = t.s[v.sg];
     const int H = S.H, W = S.W, L = S.L, NL = 1 << S.nl_log2, F = t.F, HW = H * W, mode = t.mode;
-    __shared__ MTinyGeom g; /* LDS, not registers: the level loops index it (private arrays would go to scratch) */
-    if (threadIdx.x == 0) mtiny_geom(H, W, L, F, g);
+    __shared__ wtm_tiny_geom g;
+    if (threadIdx.x == 0) wtm_tiny_geometry(H, W, L, F, g);
     __syncthreads();
-    const int PP = g.PR * g.PC;
-    const int64_t b0 = (int64_t)w * NL;
-    const int nimg = (int)(S.B - b0 < NL ? S.B - b0 : NL);
-    const int lane = threadIdx.x;
+    const int PP = g.PR * g.PC, lane = threadIdx.x;
     float* A = lds;
     float* T = A + wtm_tiny_area_a(H, W, L, F) * NL;
     float* D = T + wtm_tiny_area_t(H, W, L, F) * NL;
-    const float* in = S.in + b0 * HW;
-    for (int e = lane; e < nimg * HW; e += MT_THREADS) {
-        const int img = e / HW, s = e - img * HW;
-        A[s * NL + img] = in[e];
-    }
+    tiny_load(A, NL, S.in + v.b0 * HW, v.nimg, HW, [](float x) { return x; });
     if (lane < NL)
         for (int s = 0; s < PP; ++s) D[s * NL + lane] = 0.0f;
     __syncthreads();
-    if (lane < nimg) {
-        float* a = A + lane;
-        float* tt = T + lane;
-        float* dd = D + lane;
-        const float *dlo = ltap, *dhi = ltap + MT_F_MAX;
-        for (int k = 1; k <= L; ++k) {
-            const int R0 = g.R[k - 1], C0 = g.C[k - 1], R = g.R[k], C = g.C[k];
-            for (int c = 0; c < C0; ++c)
-                for (int o = 0; o < R; ++o) {
-                    float sa, sd;
-                    wtm_ana_point(o, R0, F, dlo, dhi, mode, [&](int64_t q) { return a[((int)q * C0 + c) * NL]; }, sa, sd);
-                    tt[(o * C0 + c) * NL] = sa;
-                    tt[((R + o) * C0 + c) * NL] = sd;
-                }
-            const int last = k == L;
-            for (int r = 0; r < R; ++r)
-                for (int o = 0; o < C; ++o) {
-                    float aa, ad, da, d2;
-                    wtm_ana_point(o, C0, F, dlo, dhi, mode, [&](int64_t q) { return tt[(r * C0 + (int)q) * NL]; }, aa, ad);
-                    wtm_ana_point(o, C0, F, dlo, dhi, mode, [&](int64_t q) { return tt[((R + r) * C0 + (int)q) * NL]; },
-                                  da, d2);
-                    if (last) dd[(r * g.PC + o) * NL] = aa;
-                    else a[(r * C + o) * NL] = aa;
-                    dd[(r * g.PC + g.offC[k] + o) * NL] = ad;
-                    dd[((g.offR[k] + r) * g.PC + o) * NL] = da;
-                    dd[((g.offR[k] + r) * g.PC + g.offC[k] + o) * NL] = d2;
-                }
-        }
-    }
+    if (lane < v.nimg) wtm_tiny_fwd(A + lane, T + lane, D + lane, NL, g, L, F, mode, ltap, ltap + WTM_TINY_F_MAX);
     __syncthreads();
-    float* P = S.P + b0 * PP;
-    for (int e = lane; e < nimg * PP; e += MT_THREADS) {
-        const int img = e / PP, s = e - img * PP;
-        P[e] = D[s * NL + img];
-    }
+    tiny_store(S.P + v.b0 * PP, D, NL, v.nimg, PP, [](float) {});
 }
 
-__global__ __launch_bounds__(MT_THREADS) void k_mtiny_inv(MTinyTable t) {
-    __shared__ float lds[MT_WAVE_WORDS];
-    __shared__ float ltap[4 * MT_F_MAX];
-    int sg, w;
-    mtiny_setup(t, ltap, sg, w);
-    const MTinySeg& S = t.s[sg];
+__global__ __launch_bounds__(TINY_THREADS) void k_mtiny_inv(MTinyTable t) {
+    __shared__ float lds[WTM_WAVE_WORDS];
+    __shared__ float ltap[4 * WTM_TINY_F_MAX];
+    const TinyWave v = tiny_wave(t);
+    tiny_stage_taps(ltap, WTM_TINY_F_MAX, WTM_TINY_F_MAX, [&](int k, int j) { return t.f[k][j]; });
+    const MTinySeg& S = t.s[v.sg];
     const int H = S.H, W = S.W, L = S.L, NL = 1 << S.nl_log2, F = t.F, HW = H * W;
-    __shared__ MTinyGeom g; /* LDS, not registers: the level loops index it (private arrays would go to scratch) */
-    if (threadIdx.x == 0) mtiny_geom(H, W, L, F, g);
+    __shared__ wtm_tiny_geom g;
+    if (threadIdx.x == 0) wtm_tiny_geometry(H, W, L, F, g);
     __syncthreads();
-    const int PP = g.PR * g.PC;
-    const int64_t b0 = (int64_t)w * NL;
-    const int nimg = (int)(S.B - b0 < NL ? S.B - b0 : NL);
-    const int lane = threadIdx.x;
+    const int PP = g.PR * g.PC, lane = threadIdx.x;
     const float thr = S.thr ? *S.thr : 0.0f; /* |c| < 0 never holds: no threshold */
     float* A = lds;
     float* T = A + wtm_tiny_area_a(H, W, L, F) * NL;
     float* D = T + wtm_tiny_area_t(H, W, L, F) * NL;
-    const float* P = S.P + b0 * PP;
-    for (int e = lane; e < nimg * PP; e += MT_THREADS) {
-        const int img = e / PP, s = e - img * PP;
-        D[s * NL + img] = mthr_load(P[e], thr);
-    }
+    tiny_load(D, NL, S.P + v.b0 * PP, v.nimg, PP, [&](float c) { return wt_thr_mask(c, thr); });
     __syncthreads();
-    if (lane < nimg) {
-        float* a = A + lane;
-        float* tt = T + lane;
-        const float* dd = D + lane;
-        const float *rlo = ltap + 2 * MT_F_MAX, *rhi = ltap + 3 * MT_F_MAX;
-        for (int k = L; k >= 1; --k) {
-            const int R = g.R[k], C = g.C[k], oH = g.R[k - 1], oW = g.C[k - 1];
-            const float* ca = (k == L) ? dd : a;
-            const int lda = (k == L) ? g.PC : C;
-            const float* pad = dd + g.offC[k] * NL;
-            const float* pda = dd + g.offR[k] * g.PC * NL;
-            const float* pdd = dd + (g.offR[k] * g.PC + g.offC[k]) * NL;
-            for (int r = 0; r < R; ++r)
-                for (int n = 0; n < oW; ++n) {
-                    tt[(r * oW + n) * NL] =
-                        wtm_syn_point(n, F, rlo, rhi, [&](int64_t q) { return ca[(r * lda + (int)q) * NL]; },
-                                      [&](int64_t q) { return pad[(r * g.PC + (int)q) * NL]; });
-                    tt[((R + r) * oW + n) * NL] =
-                        wtm_syn_point(n, F, rlo, rhi, [&](int64_t q) { return pda[(r * g.PC + (int)q) * NL]; },
-                                      [&](int64_t q) { return pdd[(r * g.PC + (int)q) * NL]; });
-                }
-            for (int m = 0; m < oH; ++m)
-                for (int n = 0; n < oW; ++n)
-                    a[(m * oW + n) * NL] =
-                        wtm_syn_point(m, F, rlo, rhi, [&](int64_t q) { return tt[((int)q * oW + n) * NL]; },
-                                      [&](int64_t q) { return tt[((R + (int)q) * oW + n) * NL]; });
-        }
-    }
+    if (lane < v.nimg)
+        wtm_tiny_inv(A + lane, T + lane, D + lane, NL, g, L, F, ltap + 2 * WTM_TINY_F_MAX, ltap + 3 * WTM_TINY_F_MAX);
     __syncthreads();
-    float* out = S.out + b0 * HW;
     unsigned z = 0;
-    for (int e = lane; e < nimg * HW; e += MT_THREADS) {
-        const int img = e / HW, s = e - img * HW;
-        const float v = A[s * NL + img];
-        out[e] = v;
-        z += (v == 0.0f);
-    }
+    tiny_store(S.out + v.b0 * HW, A, NL, v.nimg, HW, [&](float y) { z += (y == 0.0f); });
     z = wave_sum_u32(z);
     if (lane == 0 && z && S.zc) atomicAdd(S.zc, (unsigned long long)z);
 }
@@ -307,10 +206,10 @@ void launch_midwt_level(const float* a, int a_from_P, const float* P, int64_t PR
 }
 
 void launch_mtiny_fwd(const MTinyTable& t, hipStream_t s) {
-    hipLaunchKernelGGL(k_mtiny_fwd, dim3((unsigned)t.nwave), dim3(MT_THREADS), 0, s, t);
+    hipLaunchKernelGGL(k_mtiny_fwd, dim3((unsigned)t.nwave), dim3(TINY_THREADS), 0, s, t);
 }
 void launch_mtiny_inv(const MTinyTable& t, hipStream_t s) {
-    hipLaunchKernelGGL(k_mtiny_inv, dim3((unsigned)t.nwave), dim3(MT_THREADS), 0, s, t);
+    hipLaunchKernelGGL(k_mtiny_inv, dim3((unsigned)t.nwave), dim3(TINY_THREADS), 0, s, t);
 }
 
 }  // namespace wtp

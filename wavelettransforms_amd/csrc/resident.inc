@@ -151,7 +151,7 @@ __device__ __forceinline__ void res_final(const float4 (&v)[RES_IT], float thr, 
     constexpr int CT = RES_THREADS, IT = RES_IT;
     const int tid = threadIdx.x;
     float* qo = sd.out + base;
-    auto fin = [&](float xv) { return (fabsf(xv) < thr) ? 0.0f : xv; };
+    auto fin = [&](float xv) { return wt_thr_mask(xv, thr); };
     if (FULL) {
         float4* q4 = reinterpret_cast<float4*>(qo);
 #pragma unroll
@@ -248,7 +248,7 @@ __device__ __forceinline__ void res_pending_stores(const float4 (&v)[RES_IT], ui
                                                    const SegDesc& sd, int64_t base, int len, bool al) {
     float* qo = sd.out + base;
     const __amdgpu_buffer_rsrc_t rr = ragged_rsrc(qo, FULL ? 0 : len);
-    auto fin = [&](float xv) { return (fabsf(xv) < thr) ? 0.0f : xv; };
+    auto fin = [&](float xv) { return wt_thr_mask(xv, thr); };
     pend = __builtin_amdgcn_readfirstlane(pend); /* wave-uniform: scalar branches below */
 #pragma unroll
     for (int it = 0; it < RES_IT; ++it)

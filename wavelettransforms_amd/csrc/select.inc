@@ -622,7 +622,7 @@ __global__ __launch_bounds__(STREAM_THREADS) void k_mask_select(SegTable t, cons
     float* q = sd.out + base;
     unsigned long long z = 0;
     auto f = [&](float xv) {
-        const float y = (fabsf(xv) < thr) ? 0.0f : xv;
+        const float y = wt_thr_mask(xv, thr);
         z += y == 0.0f;
         return y;
     };

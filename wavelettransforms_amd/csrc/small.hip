@@ -697,7 +697,7 @@ __global__ __launch_bounds__(SM_THREADS) void k_small(SmallTable t, SelHeader* _
     double thr = (gm >= 0.5) ? (double)fb - (double)diff * (1.0 - gm) : (double)fa + (double)diff * gm;
     if (mk > 0x7F800000u) thr = __longlong_as_double(0x7FF8000000000000ll); /* NaN present: np.percentile is NaN */
     const float thr32 = (float)thr;
-    auto tl = [&](float c) { return (fabsf(c) < thr32) ? 0.0f : c; };
+    auto tl = [&](float c) { return wt_thr_mask(c, thr32); };
 
     /* ---------------- I: synthesis of the owned output block ---------------- */
     /* the np.where of :31 is applied as the packed coefficients are read below (tA: the cA plane

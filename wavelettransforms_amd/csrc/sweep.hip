@@ -229,7 +229,7 @@ __global__ __launch_bounds__(SW_THREADS) void k_sweep_mask(SwMaskTable t, const 
         const float th = thr[(size_t)k * t.ntensors + sg.t];
         float* q = sg.out[k] + base;
         uint32_t z = 0;
-        auto f = [&](float xv) { return (fabsf(xv) < th) ? 0.0f : xv; };
+        auto f = [&](float xv) { return wt_thr_mask(xv, th); };
         if (full) {
             float4* q4 = reinterpret_cast<float4*>(q);
 #pragma unroll

@@ -1,8 +1,8 @@
 /* One tiny image (at most 8 x 8) through the absolute-threshold method, entirely in a small
  * arena: all levels forward, the mask, all levels inverse, the crop
  * (ResNet/dwt_pruning_NoEntropy.py:41-52).  Shared by k_abs_tiny (abs.hip: the arena is LDS, one
- * image per lane, word s of an image at arena[s * NL + lane]) and the host-side check
- * (tests/native/abscore.cpp: NL = 1).
+ * image per lane, word s of an image at arena[s * NL + lane]; wt_tiny_arena.h) and the host-side
+ * check (tests/native/abscore.cpp: NL = 1 and 4).
  *
  * The levels are unclamped, so lines are shorter than the filter (a 3 x 3 kernel under an 8-tap
  * filter at level 5 ends in four 1 -> 1 levels) and every tap wraps, often more than once.  Every
@@ -16,9 +16,7 @@
 #ifndef WT_ABS_CORE_H
 #define WT_ABS_CORE_H
 
-#include <math.h>
-
-#include "wt_dwt_core.h"
+#include "wt_tiny_arena.h"
 
 /* t mod m for m in {1, 2, 3, 4, 6, 8} and |t| <= 128 (F <= 102 taps, lines of at most 8 samples),
  * inv = abs_inv(m): a multiply and a shift, no division and no branch */
@@ -120,9 +118,6 @@ WT_CORE float abs_syn(int n, int N, int F, const float* rlo, const float* rhi, c
     return acc;
 }
 
-/* np.where(|c| < thr32, 0, c): false for a NaN on either side */
-WT_CORE float abs_mask(float c, float thr) { return (fabsf(c) < thr) ? 0.0f : c; }
-
 /* level k of an H x W image: its size and the word offset of its three detail blocks in the
  * coefficient area ([cA_L | details of level 1 | level 2 | ...], no padding cells) */
 WT_CORE void abs_level(int k, int H, int W, int ca_words, int& R, int& C, int& doff) {
@@ -159,18 +154,14 @@ WT_CORE int abs_area_d(int H, int W, int L) {
 WT_CORE int abs_tiny_words(int H, int W, int L) { return abs_area_a(H, W, L) + abs_area_t(H, W, L) + abs_area_d(H, W, L); }
 
 /* A wave of k_abs_tiny has 16 KB of LDS: its copy of the four filters (ABS_TAP_WORDS) and the
- * arena (ABS_WAVE_WORDS).  It takes 64 images, one per lane, unless their areas do not fit the
- * arena: then 32, 16, ... (the other lanes idle).  Returns log2 of the lanes used, -1 when the
- * image is not a tiny one (a side above ABS_SIDE_MAX, or one image alone does not fit). */
+ * arena (ABS_WAVE_WORDS).  Returns log2 of the lanes used (tiny_lanes_log2), -1 when the image is
+ * not a tiny one (a side above ABS_SIDE_MAX, or one image alone does not fit). */
 #define ABS_SIDE_MAX 8
 #define ABS_TAP_WORDS (4 * ((WTP_MAX_F + 1) / 2 * 2))
 #define ABS_WAVE_WORDS (4096 - ABS_TAP_WORDS)
 WT_CORE int abs_lanes_log2(int64_t H, int64_t W, int L) {
     if (H < 1 || W < 1 || H > ABS_SIDE_MAX || W > ABS_SIDE_MAX || L < 0) return -1;
-    const int words = abs_tiny_words((int)H, (int)W, L);
-    int lg = 6;
-    while (lg > 0 && (words << lg) > ABS_WAVE_WORDS) --lg;
-    return (words << lg) <= ABS_WAVE_WORDS ? lg : -1;
+    return tiny_lanes_log2(abs_tiny_words((int)H, (int)W, L), ABS_WAVE_WORDS);
 }
 
 /* a, tt, dd: the image's word 0 of the areas A (holding the H x W image), T and D; NL: the
@@ -178,7 +169,7 @@ WT_CORE int abs_lanes_log2(int64_t H, int64_t W, int L) {
 WT_CORE void abs_image(float* a, float* tt, float* dd, int NL, int H, int W, int L, int F, const float* dlo,
                        const float* dhi, const float* rlo, const float* rhi, float thr) {
     if (L == 0) {
-        for (int s = 0; s < H * W; ++s) a[s * NL] = abs_mask(a[s * NL], thr);
+        for (int s = 0; s < H * W; ++s) a[s * NL] = wt_thr_mask(a[s * NL], thr);
         return;
     }
     int RL, CL, unused;
@@ -202,11 +193,11 @@ WT_CORE void abs_image(float* a, float* tt, float* dd, int NL, int H, int W, int
                 abs_ana2(o, C0, F, dlo, dhi, [&](int q) { return tt[(r * C0 + q) * NL]; },
                          [&](int q) { return tt[((R + r) * C0 + q) * NL]; }, aa, ad, da, d2);
                 const int x = r * C + o;
-                if (last) dd[x * NL] = abs_mask(aa, thr);
+                if (last) dd[x * NL] = wt_thr_mask(aa, thr);
                 else a[x * NL] = aa;
-                dd[(doff + x) * NL] = abs_mask(ad, thr);
-                dd[(doff + R * C + x) * NL] = abs_mask(da, thr);
-                dd[(doff + 2 * R * C + x) * NL] = abs_mask(d2, thr);
+                dd[(doff + x) * NL] = wt_thr_mask(ad, thr);
+                dd[(doff + R * C + x) * NL] = wt_thr_mask(da, thr);
+                dd[(doff + 2 * R * C + x) * NL] = wt_thr_mask(d2, thr);
             }
         doff += 3 * R * C;
         R0 = R;

@@ -19,6 +19,7 @@
 #ifndef WT_DWT_CORE_H
 #define WT_DWT_CORE_H
 
+#include <math.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -33,6 +34,9 @@ WT_CORE int64_t wt_pmod(int64_t a, int64_t m) {
     int64_t r = a % m;
     return r < 0 ? r + m : r;
 }
+
+/* the threshold rule, np.where(|c| < thr32, 0, c): false for a NaN on either side */
+WT_CORE float wt_thr_mask(float c, float thr) { return (fabsf(c) < thr) ? 0.0f : c; }
 
 /* index into a periodized line of N samples extended to even length (odd N repeats x[N-1]) */
 WT_CORE int64_t wt_ext_index(int64_t t, int64_t N) {
@@ -140,10 +144,12 @@ struct wt_level_geom {
     int64_t PR, PC;             /* packed image size */
 };
 
-WT_CORE void wt_geom(int64_t H, int64_t W, int L, wt_level_geom* g) {
+/* F = 2: the periodized bank, ceil(N / 2) a level; an extension mode's F-tap bank gives
+ * floor((N + F - 1) / 2) and stacks its blocks the same way (wtm_geom of wt_modes_core.h) */
+WT_CORE void wt_geom(int64_t H, int64_t W, int L, wt_level_geom* g, int F = 2) {
     g->R[0] = H;
     g->C[0] = W;
-    for (int k = 1; k <= L; ++k) { g->R[k] = (g->R[k - 1] + 1) / 2; g->C[k] = (g->C[k - 1] + 1) / 2; }
+    for (int k = 1; k <= L; ++k) { g->R[k] = (g->R[k - 1] + F - 1) / 2; g->C[k] = (g->C[k - 1] + F - 1) / 2; }
     int64_t aR = g->R[L], aC = g->C[L];
     for (int k = L; k >= 1; --k) { g->offR[k] = aR; g->offC[k] = aC; aR += g->R[k]; aC += g->C[k]; }
     g->PR = (L == 0) ? H : aR;

@@ -1,6 +1,7 @@
 /* One level of PyWavelets' float32 filter bank under the signal-extension modes zero, constant,
- * symmetric, reflect and periodic (every mode but periodization, which wt_dwt_core.h holds), and
- * the geometry of wavedec2 / coeffs_to_array / waverec2 under them.  Shared by the HIP kernels
+ * symmetric, reflect and periodic (every mode but periodization, which wt_dwt_core.h holds), the
+ * geometry of wavedec2 / coeffs_to_array / waverec2 under them, and the tiny-image kernels'
+ * per-image routines (wtm_tiny_fwd / wtm_tiny_inv, at the end).  Shared by the HIP kernels
  * (modes.hip) and the host-side check (tests/native/modescore.cpp).  GATHER forms, each output
  * summed in exactly the order pywt's C code sums it (separate multiply and add -- build with
  * -ffp-contract=off).  The rule was established against pywt.dwt / pywt.idwt bit for bit
@@ -29,7 +30,7 @@
 #ifndef WT_MODES_CORE_H
 #define WT_MODES_CORE_H
 
-#include "wt_dwt_core.h"
+#include "wt_tiny_arena.h"
 
 /* == WTP_MODE_* of wtprune.h */
 #define WTM_PERIODIZATION 0
@@ -131,17 +132,7 @@ WT_CORE float wtm_syn_point(int64_t n, int F, const float* rlo, const float* rhi
  * waverec2 drops that last row before level k - 1 (its inter-level crop), so every level WRITES
  * R[k-1] x C[k-1]; what the reference's final crop sees is wtm_out_len(R[1]). */
 WT_CORE void wtm_geom(int64_t H, int64_t W, int L, int F, int mode, wt_level_geom* g) {
-    if (mode == WTM_PERIODIZATION) {
-        wt_geom(H, W, L, g);
-        return;
-    }
-    g->R[0] = H;
-    g->C[0] = W;
-    for (int k = 1; k <= L; ++k) { g->R[k] = wtm_dec_len(g->R[k - 1], F); g->C[k] = wtm_dec_len(g->C[k - 1], F); }
-    int64_t aR = g->R[L], aC = g->C[L];
-    for (int k = L; k >= 1; --k) { g->offR[k] = aR; g->offC[k] = aC; aR += g->R[k]; aC += g->C[k]; }
-    g->PR = (L == 0) ? H : aR;
-    g->PC = (L == 0) ? W : aC;
+    wt_geom(H, W, L, g, mode == WTM_PERIODIZATION ? 2 : F);
 }
 /* whether every level's input lines can be analysed (wtm_line_ok: a two-sample line becomes a
  * one-sample line under haar, which reflect cannot extend) */
@@ -164,17 +155,31 @@ WT_CORE int64_t wtm_block_cells(const wt_level_geom* g, int L) {
     return nc;
 }
 
-
 /* ---- tiny images (both sides <= WTM_SIDE_MAX): k_mtiny_fwd / k_mtiny_inv keep one image per
- * lane in a wave's LDS arena, in words per image: A the image, a level's approximation or a
- * level's synthesis output (R[k] x C[k], k < L); T a level's two half transforms (2 R[k] x C[k-1]);
- * D the packed image.  A wave takes 64 images unless their areas do not fit its arena: then 32,
- * 16, ... (the other lanes idle).  wtm_tiny_lanes_log2: log2 of the lanes used, -1 when the
- * tensor is not a tiny one. */
+ * lane in a wave's LDS arena (wt_tiny_arena.h), in words per image: A the image, a level's
+ * approximation or a level's synthesis output (R[k] x C[k], k < L); T a level's two half
+ * transforms (2 R[k] x C[k-1]); D the packed image (PR x PC, row pitch PC).
+ * wtm_tiny_lanes_log2: log2 of the lanes used, -1 when the tensor is not a tiny one. */
 #define WTM_SIDE_MAX 8
 #define WTM_TINY_LMAX 4
 #define WTM_TINY_F_MAX 4
 #define WTM_WAVE_WORDS 8192
+/* wtm_geom of a tiny image in small ints (1 <= L <= WTM_TINY_LMAX).  The kernels keep it in LDS:
+ * the level loops index it, and indexed private arrays would go to scratch. */
+struct wtm_tiny_geom {
+    int R[WTM_TINY_LMAX + 1], C[WTM_TINY_LMAX + 1], offR[WTM_TINY_LMAX + 1], offC[WTM_TINY_LMAX + 1], PR, PC;
+};
+WT_CORE void wtm_tiny_geometry(int H, int W, int L, int F, wtm_tiny_geom& g) {
+    g.R[0] = H;
+    g.C[0] = W;
+    for (int k = 1; k <= L; ++k) { g.R[k] = (g.R[k - 1] + F - 1) >> 1; g.C[k] = (g.C[k - 1] + F - 1) >> 1; }
+    int aR = g.R[L], aC = g.C[L];
+    for (int k = L; k >= 1; --k) { g.offR[k] = aR; g.offC[k] = aC; aR += g.R[k]; aC += g.C[k]; }
+    g.PR = aR;
+    g.PC = aC;
+}
+/* The areas walk the sizes in scalars and not out of a wtm_tiny_geom: the kernels place T and D
+ * with them, and from the geometry in LDS those offsets cost vector registers. */
 WT_CORE int wtm_tiny_area_a(int H, int W, int L, int F) {
     int R = H, C = W, words = H * W;
     for (int k = 1; k < L; ++k) {
@@ -195,17 +200,78 @@ WT_CORE int wtm_tiny_area_t(int H, int W, int L, int F) {
     return words;
 }
 WT_CORE int wtm_tiny_area_d(int H, int W, int L, int F) {
-    wt_level_geom g;
-    wtm_geom(H, W, L, F, WTM_ZERO, &g);
-    return (int)(g.PR * g.PC);
+    int PR, PC;
+    tiny_packed_size(H, W, L, F, PR, PC);
+    return PR * PC;
 }
 WT_CORE int wtm_tiny_lanes_log2(int64_t H, int64_t W, int L, int F) {
     if (H < 1 || W < 1 || H > WTM_SIDE_MAX || W > WTM_SIDE_MAX || L < 1 || L > WTM_TINY_LMAX || F > WTM_TINY_F_MAX) return -1;
-    const int words = wtm_tiny_area_a((int)H, (int)W, L, F) + wtm_tiny_area_t((int)H, (int)W, L, F) +
-                      wtm_tiny_area_d((int)H, (int)W, L, F);
-    int lg = 6;
-    while (lg > 0 && (words << lg) > WTM_WAVE_WORDS) --lg;
-    return (words << lg) <= WTM_WAVE_WORDS ? lg : -1;
+    const int h = (int)H, w = (int)W;
+    const int words = wtm_tiny_area_a(h, w, L, F) + wtm_tiny_area_t(h, w, L, F) + wtm_tiny_area_d(h, w, L, F);
+    return tiny_lanes_log2(words, WTM_WAVE_WORDS);
+}
+
+/* The per-image routines of k_mtiny_fwd / k_mtiny_inv.  a, tt, dd: the image's word 0 of the
+ * areas A, T and D; NL: the word stride.
+ * wtm_tiny_fwd: every analysis level of the H x W image in A into the packed image in D (the cells
+ * no block covers are not written: the caller zero-fills D). */
+WT_CORE void wtm_tiny_fwd(float* a, float* tt, float* dd, int NL, const wtm_tiny_geom& g, int L, int F, int mode,
+                          const float* dlo, const float* dhi) {
+    const int PC = g.PC;
+    for (int k = 1; k <= L; ++k) {
+        const int R0 = g.R[k - 1], C0 = g.C[k - 1], R = g.R[k], C = g.C[k];
+        for (int c = 0; c < C0; ++c)
+            for (int o = 0; o < R; ++o) {
+                float sa, sd;
+                wtm_ana_point(o, R0, F, dlo, dhi, mode, [&](int64_t q) { return a[((int)q * C0 + c) * NL]; }, sa, sd);
+                tt[(o * C0 + c) * NL] = sa;
+                tt[((R + o) * C0 + c) * NL] = sd;
+            }
+        const int last = k == L;
+        for (int r = 0; r < R; ++r)
+            for (int o = 0; o < C; ++o) {
+                float aa, ad, da, d2;
+                wtm_ana_point(o, C0, F, dlo, dhi, mode, [&](int64_t q) { return tt[(r * C0 + (int)q) * NL]; }, aa, ad);
+                wtm_ana_point(o, C0, F, dlo, dhi, mode, [&](int64_t q) { return tt[((R + r) * C0 + (int)q) * NL]; },
+                              da, d2);
+                if (last) dd[(r * PC + o) * NL] = aa;
+                else a[(r * C + o) * NL] = aa;
+                dd[(r * PC + g.offC[k] + o) * NL] = ad;
+                dd[((g.offR[k] + r) * PC + o) * NL] = da;
+                dd[((g.offR[k] + r) * PC + g.offC[k] + o) * NL] = d2;
+            }
+    }
+}
+/* wtm_tiny_inv: every synthesis level out of the packed image in D, already thresholded, into A
+ * (H x W, row pitch W).  Level k reads cA_k from D at the top (row pitch PC), else from A where
+ * the level above left it, and writes R[k-1] x C[k-1]: waverec2's inter-level crop and, at
+ * k = 1, the final one. */
+WT_CORE void wtm_tiny_inv(float* a, float* tt, const float* dd, int NL, const wtm_tiny_geom& g, int L, int F,
+                          const float* rlo, const float* rhi) {
+    const int PC = g.PC;
+    for (int k = L; k >= 1; --k) {
+        const int R = g.R[k], C = g.C[k], oH = g.R[k - 1], oW = g.C[k - 1];
+        const float* ca = (k == L) ? dd : a;
+        const int lda = (k == L) ? PC : C;
+        const float* pad = dd + g.offC[k] * NL;
+        const float* pda = dd + g.offR[k] * PC * NL;
+        const float* pdd = dd + (g.offR[k] * PC + g.offC[k]) * NL;
+        for (int r = 0; r < R; ++r)
+            for (int n = 0; n < oW; ++n) {
+                tt[(r * oW + n) * NL] =
+                    wtm_syn_point(n, F, rlo, rhi, [&](int64_t q) { return ca[(r * lda + (int)q) * NL]; },
+                                  [&](int64_t q) { return pad[(r * PC + (int)q) * NL]; });
+                tt[((R + r) * oW + n) * NL] =
+                    wtm_syn_point(n, F, rlo, rhi, [&](int64_t q) { return pda[(r * PC + (int)q) * NL]; },
+                                  [&](int64_t q) { return pdd[(r * PC + (int)q) * NL]; });
+            }
+        for (int m = 0; m < oH; ++m)
+            for (int n = 0; n < oW; ++n)
+                a[(m * oW + n) * NL] =
+                    wtm_syn_point(m, F, rlo, rhi, [&](int64_t q) { return tt[((int)q * oW + n) * NL]; },
+                                  [&](int64_t q) { return tt[((R + (int)q) * oW + n) * NL]; });
+    }
 }
 
 #endif
+

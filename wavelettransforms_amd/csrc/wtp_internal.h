@@ -458,11 +458,10 @@ struct RandTable {
 void launch_random_prune(const RandTable& t, wtp_result* res, hipStream_t s);
 void launch_count_small(const float* x, int64_t n, float thr, unsigned long long* count, hipStream_t s);
 /* ---- the absolute-threshold method (abs.hip, wtp_prune_abs_f32) ----
- * k_abs_tiny: one wave per workgroup and per NL images of one tensor, word s of image i at
- * lds[s * NL + i]; NL = 64 unless an image's areas (abs_tiny_words) need more than the wave's
- * ABS_WAVE_WORDS / 64, then the next power of two that fits (the other lanes idle). */
+ * k_abs_tiny: one wave (TINY_THREADS) per workgroup and per NL images of one tensor in the arena
+ * of wt_tiny_arena.h, whose tiny_append fills what AbsTable and MTinyTable share: nseg, nwave,
+ * wave_begin and the head of a segment (in .. nl_log2). */
 constexpr int ABS_MAX_SEG = 64;        /* tensors per k_abs_tiny launch (the table is its kernel argument) */
-constexpr int ABS_THREADS = 64;
 /* ABS_SIDE_MAX, ABS_TAP_WORDS, ABS_WAVE_WORDS and the lane choice abs_lanes_log2: wt_abs_core.h */
 constexpr int ABS_COUNT_THREADS = 256;
 struct AbsSeg {
@@ -498,10 +497,6 @@ void launch_midwt_level(const float* a, int a_from_P, const float* P, int64_t PR
                         float* tH, float* y, int64_t oH, int64_t oW, unsigned long long* zc, hipStream_t s);
 /* k_mtiny_fwd / k_mtiny_inv: one wave per workgroup and per NL images of one tensor (the lane
  * choice wtm_tiny_lanes_log2), the tiny tensors of one launch group per launch */
-constexpr int MT_THREADS = 64;
-constexpr int MT_LMAX = WTM_TINY_LMAX;
-constexpr int MT_F_MAX = WTM_TINY_F_MAX;
-constexpr int MT_WAVE_WORDS = WTM_WAVE_WORDS;
 struct MTinySeg {
     const float* in;
     float* out;
@@ -513,7 +508,7 @@ struct MTinySeg {
 };
 struct MTinyTable {
     int32_t nseg, nwave, mode, F;
-    float f[4][MT_F_MAX];      /* dec_lo, dec_hi, rec_lo, rec_hi */
+    float f[4][WTM_TINY_F_MAX];      /* dec_lo, dec_hi, rec_lo, rec_hi */
     int32_t wave_begin[SEG_PER_LAUNCH];
     MTinySeg s[SEG_PER_LAUNCH];
 };

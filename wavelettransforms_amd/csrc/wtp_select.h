@@ -598,7 +598,7 @@ __device__ __forceinline__ unsigned long long mask_body(const SegDesc& sd, int64
     else load_chunk_ragged<16>(p, len, v);
     unsigned long long z = 0;
     auto f = [&](float xv) {
-        const float y = (fabsf(xv) < thr) ? 0.0f : xv;
+        const float y = wt_thr_mask(xv, thr);
         z += y == 0.0f;
         return y;
     };
