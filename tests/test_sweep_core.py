@@ -13,6 +13,7 @@ import pytest
 
 from oracle import oracle as O
 from tests import golden_io as G
+from tests.ref_helpers import np_ranks
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BUILD = os.path.join(HERE, "_build")
@@ -45,15 +46,6 @@ def core():
 
 def keys_of(x):
     return np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1).view(np.uint32) & np.uint32(0x7FFFFFFF))
-
-
-def np_ranks(n, pct):
-    """np.percentile's two order statistics (NumPy 1.x, linear): (r0, above, gamma)."""
-    vi = (n - 1) * (pct / 100.0)
-    if vi >= n - 1:
-        return n - 1, 1, vi + 1.0
-    fl = math.floor(vi)
-    return int(fl), 0, vi - fl
 
 
 def _u32(a):

@@ -203,7 +203,7 @@ __device__ void select_in_range(const Get& get, const Keep& keep, int64_t m, uin
     __shared__ int64_t bsel[2];
     const uint32_t diff = lo ^ hi;
     int top = diff ? 31 - __clz(diff) : -1; /* highest unknown bit */
-    const uint32_t known = top >= 31 ? 0u : ~((2u << top) - 1u);
+    const uint32_t known = top >= 31 ? 0u : (top < 0 ? 0xFFFFFFFFu : ~((2u << top) - 1u)); /* lo == hi: every bit */
     uint32_t pa = lo & known, pb = lo & known, mask = known;
     while (top >= 0) {
         const int width = top + 1 < 8 ? top + 1 : 8;
@@ -250,7 +250,7 @@ __device__ __forceinline__ uint32_t wave_select_rank(const uint32_t* stage, int 
     }
     const uint32_t diff = lo ^ hi;
     const int top = diff ? 31 - __clz(diff) : -1;
-    uint32_t res = top >= 31 ? 0u : (lo & ~((2u << top) - 1u));
+    uint32_t res = top >= 31 ? 0u : (top < 0 ? lo : (lo & ~((2u << top) - 1u))); /* lo == hi: the key itself */
     const uint32_t rr = (uint32_t)r; /* r < m */
     for (int b = top; b >= 0; --b) {
         const uint32_t cand = res | (1u << b);
