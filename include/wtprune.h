@@ -20,6 +20,8 @@
  *   wtp_prune_abs_f32               multi_resolution_analysis         dwt_pruning_NoEntropy.py:29-60
  *   wtp_prune_sweep_f32             multi_resolution_analysis at a grid of percentiles: the loop of
  *                                   main_pruning.py:186 over its thresholds, in one call
+ *   wtp_prune_abs_sweep_f32         multi_resolution_analysis of dwt_pruning_NoEntropy.py:29-60 at a
+ *                                   grid of absolute thresholds (the same loop), in one call
  *   wtp_synth_f32                   (test/bench input generator, no reference counterpart)
  */
 #ifndef WTPRUNE_H
@@ -214,6 +216,39 @@ typedef struct wtp_abs_result {   /* one per tensor, device memory */
 size_t wtp_abs_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level);
 int wtp_prune_abs_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double threshold,
                       void* workspace, size_t workspace_bytes, wtp_abs_result* results_dev, wtp_stream_t stream);
+
+/* ---- the absolute-threshold sweep: one call prunes the list at up to eight absolute thresholds
+ * (the threshold grid of ResNet/main_pruning.py under dwt_pruning_NoEntropy.py's method) ----
+ * For every k < nthr the outputs outs[k * ntensors + t] and the records
+ * results_dev[k * ntensors + t] (threshold-major: block k of the records is laid out like the
+ * records of one ordinary call) are, bit for bit and field for field (path included), what
+ * wtp_prune_abs_f32(tensors, ..., thresholds[k], ...) gives: the unclamped level, the float32
+ * rounding of the threshold (NaN, zero and negative thresholds prune nothing, +inf and 1e40 prune
+ * every finite coefficient), the generic crop, both non-zero counts (nonzero_in is counted on the
+ * input before any output is written), and the same choice among the three paths.  The method
+ * selects nothing, so a tensor is read and transformed forward ONCE and every threshold costs
+ * one mask and inverse: tiny-image tensors (path 1) keep their raw coefficients on chip and run
+ * every threshold's inverse over them in the same launch (groups of 24 tensors); a chain tensor
+ * (path 2) keeps one packed array in the workspace, read with threshold k on the load by the k-th
+ * inverse; a plain mask (path 0) is one masked copy per threshold.
+ * thresholds (host memory) may repeat and need not be sorted: every k is answered on its own.
+ * tensors[t].out is ignored and may be NULL.  AT MOST ONE output of a tensor may be the tensor's
+ * input (in place); the other outputs must not overlap it.
+ * Validation before any device work, nothing written on error: everything wtp_prune_abs_f32
+ * rejects, nthr outside [1, WTP_ABS_SWEEP_MAX_THR] or thresholds == NULL (WTP_EARG), a NULL
+ * output of a non-empty tensor (WTP_EARG), two outputs of one tensor at the same address
+ * (WTP_EARG).
+ * Workspace: wtp_abs_sweep_workspace_size bytes (0 if the request is invalid), the rules of
+ * wtp_prune_abs_f32's: no initialisation, plain scratch of this entry, NOT the workspace of the
+ * percentile entries; a call of tiny tensors only needs the same few bytes whatever its batch and
+ * nthr.  Stream-ordered, no allocation, no synchronisation, capturable. */
+#define WTP_ABS_SWEEP_MAX_THR 8
+size_t wtp_abs_sweep_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int nthr);
+int wtp_prune_abs_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level,
+                            const double* thresholds /* host */, int nthr,
+                            float* const* outs /* host array of nthr * ntensors device pointers */, void* workspace,
+                            size_t workspace_bytes, wtp_abs_result* results_dev /* nthr * ntensors */,
+                            wtp_stream_t stream);
 
 /* ---- the percentile sweep: one call prunes the list at several percentiles (the experiment of
  * ResNet/main_pruning.py:186, the same model and wavelet at a grid of thresholds) ----

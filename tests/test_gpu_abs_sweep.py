@@ -1,0 +1,307 @@
+"""GPU parity of the absolute-threshold sweep (wtp_prune_abs_sweep_f32, engine.prune_abs_sweep): every
+threshold of one sweep call against the ordinary call at that threshold (wtp_prune_abs_f32), the
+PyWavelets goldens and the C oracle.  Bar: outputs bit for bit (np.array_equal and canon_hash; the
+bit patterns where NaN can occur), records equal field for field, path included."""
+import json
+import math
+import os
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+from tests import golden_io as G
+from tests.ref_helpers import ABS_CHAIN, ABS_MASK, ABS_TINY, abs_oracle
+
+pytestmark = pytest.mark.gpu
+
+ABS = json.load(open(os.path.join(G.GOLDEN, "abs_manifest.json")))
+ARR = dict(np.load(os.path.join(G.GOLDEN, "abs_cases.npz")))
+MASK, TINY, CHAIN = ABS_MASK, ABS_TINY, ABS_CHAIN
+
+# tests/test_gpu_abs_threshold.py's tiny shapes and settings
+TINY_SHAPES = [(8, 3, 1, 1), (67, 3, 3, 3), (1, 1, 3, 3), (4, 3, 7, 7), (5, 2, 5, 5), (3, 2, 2, 3), (6, 1, 8, 8)]
+TINY_SETTINGS = [("haar", 5), ("db2", 2), ("bior3.3", 5), ("db8", 1), ("db8", 5), ("bior3.3", 0)]
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from wavelettransforms_amd import engine
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return engine
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _same(a, b, tag):
+    assert a.shape == b.shape and a.dtype == b.dtype == np.float32, tag
+    assert np.array_equal(_bits(a), _bits(b)), tag
+    assert G.canon_hash(a) == G.canon_hash(b), tag
+
+
+def _rec_equal(a, b):
+    """records equal field for field; a NaN threshold by its bits (thr32 is decoded from them)"""
+    ka = {k: v for k, v in a.items() if k != "thr32"}
+    kb = {k: v for k, v in b.items() if k != "thr32"}
+    return ka == kb
+
+
+def _cuda(xs_np):
+    return [torch.from_numpy(x).cuda() for x in xs_np]
+
+
+def _sweep_equals_calls(eng, xs_np, wavelet, level, thrs, tag):
+    """one sweep against len(thrs) ordinary calls on the same inputs; returns (outs, recs) as numpy"""
+    xs = _cuda(xs_np)
+    outs, recs = eng.prune_abs_sweep(xs, wavelet, level, thrs)
+    assert len(outs) == len(recs) == len(thrs)
+    got = [[o.cpu().numpy() for o in os_] for os_ in outs]
+    for x, v in zip(xs, xs_np):
+        assert np.array_equal(_bits(x.cpu().numpy()), _bits(v)), "out of place: the input is untouched"
+    for k, thr in enumerate(thrs):
+        o1, r1 = eng.prune_abs(xs, wavelet, level, thr)
+        for t, (a, b, ra, rb) in enumerate(zip(got[k], o1, recs[k], r1)):
+            _same(a, b.cpu().numpy(), (tag, k, thr, xs_np[t].shape))
+            assert _rec_equal(ra, rb), (tag, k, thr, xs_np[t].shape, ra, rb)
+    return got, recs
+
+
+def test_golden_cases(eng):
+    """The PyWavelets anchor.  Each (wavelet, level) group of the goldens in ONE sweep at the three
+    thresholds the goldens were made at; each case, at its own threshold, equals its stored
+    output, hash and counts."""
+    grid = [0.0125, 0.033725, 0.7]
+    groups = {}
+    for name, rec in ABS["cases"].items():
+        groups.setdefault((rec["wavelet"], rec["level"]), []).append(name)
+        assert rec["threshold"] in grid
+    assert len(groups) == 17
+    for (wavelet, level), names in sorted(groups.items()):
+        recs = [ABS["cases"][n] for n in names]
+        xs_np = [ARR[n + "/in"] if n + "/in" in ARR else G.W.synth_numpy(tuple(r["shape"]), *r["synth"])
+                 for n, r in zip(names, recs)]
+        outs, res = eng.prune_abs_sweep(_cuda(xs_np), wavelet, level, grid)
+        for t, (n, rec) in enumerate(zip(names, recs)):
+            k = grid.index(rec["threshold"])
+            out, r = outs[k][t].cpu().numpy(), res[k][t]
+            _same(out, ARR[n + "/out"], n)
+            assert G.canon_hash(out) == rec["out_hash"], n
+            assert (r["nonzero_in"], r["nonzero_out"]) == (rec["nonzero_in"], rec["nonzero_out"]), n
+            assert r["thr32_bits"] == rec["thr32_bits"], n
+            assert r["coeff_numel"] == int(np.prod(rec["packed_shape"])), n
+            assert r["numel"] == xs_np[t].size, n
+            for kk in range(3):  # the other thresholds' records of this tensor: the same input count
+                assert res[kk][t]["nonzero_in"] == rec["nonzero_in"] and res[kk][t]["thr32_bits"] == G.f32_bits(grid[kk])
+
+
+@pytest.mark.parametrize("wavelet,level", TINY_SETTINGS)
+def test_sweep_equals_calls_equals_oracle(eng, wavelet, level):
+    """All tiny shapes of a setting and a 1-D (64,) tensor, eight thresholds unsorted with a
+    duplicate: sigma x [2, 0, 0.6745, 0.3, 0.6745], +inf, NaN, -1."""
+    sigma = G.W.conv_sigma((67, 3, 3, 3))
+    e = G.W.sigma_exponent(sigma)
+    xs_np = [G.W.synth_numpy(s, 71, i, e) for i, s in enumerate(TINY_SHAPES + [(64,)])]
+    thrs = [sigma * f for f in (2, 0, 0.6745, 0.3, 0.6745)] + [float("inf"), float("nan"), -1.0]
+    got, recs = _sweep_equals_calls(eng, xs_np, wavelet, level, thrs, (wavelet, level))
+    for k, thr in enumerate(thrs):
+        assert [r["path"] for r in recs[k]] == [TINY] * len(TINY_SHAPES) + [MASK]
+        for x, o, r in zip(xs_np, got[k], recs[k]):
+            ref = abs_oracle(x, wavelet, level, thr)
+            _same(o, ref, (wavelet, level, k, x.shape))
+            assert r["nonzero_in"] == int(np.count_nonzero(x)) and r["nonzero_out"] == int(np.count_nonzero(ref))
+            assert r["thr32_bits"] == G.f32_bits(thr)
+            assert r["level"] == (level if x.ndim >= 2 else 0)
+    assert not any(o.any() for o in got[5]) and all(r["nonzero_out"] == 0 for r in recs[5])  # +inf
+    # a guard of the test's own inputs, on the oracle alone: at 0.6745 sigma the threshold zeroes
+    # some but not nearly all of the packed cells
+    for x in xs_np[:-1]:
+        share = float((np.abs(O.wavedec2_packed(x, wavelet, level)) < np.float32(0.6745 * sigma)).mean())
+        assert 0.1 < share < 0.98, x.shape
+
+
+@pytest.mark.parametrize("shape,wavelet,level,path", [
+    ((64, 8), "db8", 3, CHAIN),
+    ((33, 17), "db4", 2, CHAIN),
+    ((256, 256), "db8", 8, CHAIN),
+    ((2, 96, 100), "bior3.3", 3, CHAIN),
+    ((128, 784), "rbio2.2", 3, CHAIN),
+    ((3, 2, 8, 8), "db2", 3, TINY),
+    ((3, 2, 8, 9), "db2", 3, CHAIN),
+    ((3, 2, 9, 9), "db2", 3, CHAIN),
+])
+def test_chain_and_limit_shapes(eng, shape, wavelet, level, path):
+    sigma = 1.0 / math.sqrt(shape[-1])
+    x = G.W.synth_numpy(shape, 73, 0, G.W.sigma_exponent(sigma))
+    thrs = [sigma * f for f in (0.3, 0.6745, 2)]
+    got, recs = _sweep_equals_calls(eng, [x], wavelet, level, thrs, (shape, wavelet, level))
+    pr, pc = O.packed_shape(shape[-2], shape[-1], level)
+    for k, thr in enumerate(thrs):
+        ref = abs_oracle(x, wavelet, level, thr)
+        _same(got[k][0], ref, (shape, k))
+        r = recs[k][0]
+        assert r["path"] == path and r["level"] == level
+        assert r["nonzero_in"] == int(np.count_nonzero(x)) and r["nonzero_out"] == int(np.count_nonzero(ref))
+        assert r["coeff_numel"] == x.size // (shape[-2] * shape[-1]) * pr * pc
+
+
+def test_more_tensors_than_a_launch_table(eng):
+    """The 150-tensor list of test_more_tiny_tensors_than_one_launch_table (1-D and chain tensors
+    between the tiny ones): several k_abs_tiny_sweep launches, whose wave numbering restarts while
+    the record indices run on, at eight thresholds."""
+    e = G.W.sigma_exponent(0.05)
+    shapes = []
+    for i in range(150):
+        shapes.append([(3 + i % 5, 2, 3, 3), (2, 1 + i % 3, 7, 7), (70 + i, 1, 1, 1), (1, 1, 2, 5)][i % 4])
+        if i in (10, 63, 64, 127, 128):
+            shapes.append((17,) if i % 2 else (9, 11))
+    xs_np = [G.W.synth_numpy(s, 76, i, e) for i, s in enumerate(shapes)]
+    thrs = [0.0337, 0.1, 0.0, 0.0125, 0.05, 0.0337, float("inf"), 0.02]
+    _, recs = _sweep_equals_calls(eng, xs_np, "bior3.3", 5, thrs, "150 tiny")
+    for k in range(len(thrs)):
+        assert sum(r["path"] == TINY for r in recs[k]) == 150
+
+
+def _mixed_inputs():
+    shapes = [(67, 3, 3, 3), (33, 17), (64,), (4, 3, 7, 7), (3, 2, 8, 9), (130, 5, 1, 1)]
+    e = G.W.sigma_exponent(0.05)
+    return [G.W.synth_numpy(s, 74, i, e) for i, s in enumerate(shapes)]
+
+
+@pytest.mark.parametrize("setting", ["mixed", "level0"])
+def test_in_place_equals_out_of_place(eng, setting):
+    """The inputs as output set 0 of 3: every set equals the out-of-place run's, and so do the
+    records (nonzero_in is counted before any output is written).  level0: (3, 2, 9, 9) and (64,)
+    take the mask path, which reads the input for every threshold."""
+    if setting == "mixed":
+        xs_np, wavelet, level = _mixed_inputs(), "bior3.3", 5
+    else:
+        e = G.W.sigma_exponent(0.05)
+        xs_np = _mixed_inputs() + [G.W.synth_numpy(s, 78, i, e) for i, s in enumerate([(3, 2, 9, 9), (64,)])]
+        wavelet, level = "bior3.3", 0
+    thrs = [0.0337, 0.0125, 0.1]
+    outs, recs = eng.prune_abs_sweep(_cuda(xs_np), wavelet, level, thrs)
+    if setting == "level0":
+        assert [r["path"] for r in recs[0][-2:]] == [MASK, MASK]
+    ys = _cuda(xs_np)
+    sets = [ys] + [[torch.empty_like(y) for y in ys] for _ in range(2)]
+    outs2, recs2 = eng.prune_abs_sweep(ys, wavelet, level, thrs, outs=sets)
+    assert all(a is b for a, b in zip(outs2[0], ys))
+    for k in range(3):
+        for a, b, x in zip(outs[k], outs2[k], xs_np):
+            _same(a.cpu().numpy(), b.cpu().numpy(), (setting, k, x.shape))
+    assert recs2 == recs
+    for x, r in zip(xs_np, recs2[2]):
+        assert r["nonzero_in"] == int(np.count_nonzero(x))
+
+
+def test_graph_capture_replays_on_refreshed_inputs(eng):
+    thrs = [0.0337, 0.0, 0.1]
+    a_np, b_np = _mixed_inputs(), [x[::-1].copy() if x.ndim == 1 else -x for x in _mixed_inputs()]
+    ref_a = eng.prune_abs_sweep(_cuda(a_np), "db2", 3, thrs)
+    ref_b = eng.prune_abs_sweep(_cuda(b_np), "db2", 3, thrs)
+    xs = _cuda(a_np)
+    outs = [[torch.empty_like(x) for x in xs] for _ in thrs]
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):  # warm-up: the workspace exists before the capture
+        eng.launch_abs_sweep(xs, "db2", 3, thrs, outs=outs, stream=s)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        with torch.cuda.graph(g, stream=s):
+            _, resd = eng.launch_abs_sweep(xs, "db2", 3, thrs, outs=outs)
+    n = len(xs)
+    for inputs, (ref_outs, ref_res) in ((b_np, ref_b), (a_np, ref_a)):
+        for x, v in zip(xs, inputs):
+            x.copy_(torch.from_numpy(v))
+        for os_ in outs:
+            for o in os_:
+                o.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        blocks = resd.view(len(thrs), -1)
+        assert [eng.decode_abs(blocks[k], n) for k in range(len(thrs))] == ref_res
+        for k in range(len(thrs)):
+            for o, r in zip(outs[k], ref_outs[k]):
+                assert np.array_equal(o.cpu().numpy(), r.cpu().numpy())
+
+
+def test_percentile_calls_around_an_abs_sweep(eng):
+    """The percentile entries keep selection and barrier state at the start of their workspace; the
+    sweep uses its workspace as plain scratch, and the engine gives it the abs kind's own."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ts = G.W.resnet18_tensors(0)[1:7]
+    conv_np = [G.W.synth_numpy(s, seed, tid, e) for _, s, seed, tid, e in ts]
+    abs_np = [G.W.synth_numpy(s, 77, 1 + i, G.W.sigma_exponent(0.05))
+              for i, s in enumerate([(128, 784), (33, 17), (301,), (64, 3, 3, 3)])]
+
+    def percentile_round():
+        got = []
+        outs, res = eng.prune(_cuda(conv_np), "bior3.3", 5, 50.0, carry_level=False)
+        for x, o, r in zip(conv_np, outs, res):
+            ref, rr = O.prune_tensor(x, "bior3.3", 5, 50.0)
+            assert np.array_equal(o.cpu().numpy(), ref), x.shape
+            assert r["zero_count"] == rr["zero_count"] and G.f64_bits_equal(r["thr64"], rr["thr64"])
+            got.append((o.cpu().numpy(), r))
+        return got
+
+    first = percentile_round()
+    ws = eng.workspace(dev, 256)
+    _sweep_equals_calls(eng, abs_np, "db4", 2, [0.0337, 0.1], "between percentile calls")
+    assert eng.workspace(dev, 256) is ws, "the percentile workspace is the one from before the sweep"
+    assert eng.workspace(dev, 256, kind="abs").data_ptr() != ws.data_ptr()
+    second = percentile_round()
+    for (o1, r1), (o2, r2) in zip(first, second):
+        assert np.array_equal(o1, o2) and r1 == r2
+
+
+@pytest.fixture(scope="module")
+def resnet_inputs():
+    ts = G.W.resnet18_tensors(0)
+    return ts, [G.W.synth_numpy(s, seed, tid, e) for _, s, seed, tid, e in ts]
+
+
+def test_mirror_sweep_equals_a_loop(eng, resnet_inputs):
+    from wavelettransforms_amd import dwt_pruning_NoEntropy as D
+    _, xs_np = resnet_inputs
+    ws = [torch.from_numpy(xs_np[i]) for i in (0, 1, 5)] + [torch.from_numpy(xs_np[1][0, 0, 0]).cuda()]
+    thrs = [0.0125, 0.00125, 0.05]
+    with pytest.warns(UserWarning, match="Level value of 5 is too high: all coefficients will experience boundary effects."):
+        swept = D.multi_resolution_analysis_sweep(ws, "bior3.3", 5, thrs)
+    assert len(swept) == 3
+    for thr, (outs, total) in zip(thrs, swept):
+        with pytest.warns(UserWarning, match="too high"):
+            ref_outs, ref_total = D.multi_resolution_analysis(ws, "bior3.3", 5, thr)
+        assert total == ref_total and isinstance(total, int) and total > 0
+        for w, o, r in zip(ws, outs, ref_outs):
+            assert o.device == w.device and o.dtype == w.dtype and o.shape == w.shape
+            assert np.array_equal(o.cpu().numpy(), r.cpu().numpy())
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")  # level 1 of a 7 x 7 kernel under haar is within dwt_max_level
+        D.multi_resolution_analysis_sweep(ws[:1], "haar", 1, thrs)
+
+
+def test_resnet18_one_sweep(eng, resnet_inputs):
+    """The headline workload: the whole conv list, bior3.3 level 5, three thresholds in one call;
+    GPU against GPU at each, and against the oracle at 0.0125 (about 6 s of CPU)."""
+    ts, xs_np = resnet_inputs
+    xs = [eng.synth(s, seed, tid, e) for _, s, seed, tid, e in ts]
+    thrs = [0.00125, 0.0125, 0.05]
+    outs, recs = eng.prune_abs_sweep(xs, "bior3.3", 5, thrs)
+    for k, thr in enumerate(thrs):
+        o1, r1 = eng.prune_abs(xs, "bior3.3", 5, thr)
+        for (name, *_), a, b, ra, rb in zip(ts, outs[k], o1, recs[k], r1):
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32)), (name, thr)
+            assert ra == rb, (name, thr)
+            assert ra["path"] == TINY and ra["level"] == 5, name
+    for (name, *_), x, o, r in zip(ts, xs_np, outs[1], recs[1]):
+        ref = abs_oracle(x, "bior3.3", 5, 0.0125)
+        _same(o.cpu().numpy(), ref, name)
+        assert r["nonzero_in"] == int(np.count_nonzero(x)) and r["nonzero_out"] == int(np.count_nonzero(ref)), name
+        assert r["numel"] == x.size and r["thr32_bits"] == G.f32_bits(0.0125), name

@@ -86,6 +86,9 @@ def lib():
             "wtp_waverec2_mode_f32": ([vp, vp, i64, i64, i64, i32, i32, i32, vp, vp, sz, vp], i32),
             "wtp_abs_workspace_size": ([tp, i32, i32, i32], sz),
             "wtp_prune_abs_f32": ([tp, i32, i32, i32, f64, vp, sz, vp, vp], i32),
+            "wtp_abs_sweep_workspace_size": ([tp, i32, i32, i32, i32], sz),
+            "wtp_prune_abs_sweep_f32": ([tp, i32, i32, i32, ctypes.POINTER(f64), i32, ctypes.POINTER(vp), vp, sz, vp,
+                                         vp], i32),
             "wtp_sweep_workspace_size": ([tp, i32, i32, i32, i32, i32], sz),
             "wtp_prune_sweep_f32": ([tp, i32, i32, i32, ctypes.POINTER(f64), i32, i32, ctypes.POINTER(vp), vp, sz, vp,
                                      vp], i32),

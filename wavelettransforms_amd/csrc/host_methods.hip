@@ -1,6 +1,6 @@
 /*
  * host_methods.hip -- the entries beside the percentile path: min-weight pruning, random pruning,
- * the sparsity count, the absolute-threshold method, the transform components and the synthetic
+ * the sparsity count, the absolute-threshold method and its sweep, the transform components and the synthetic
  * inputs.  Each validates with its own rules on top of read_shape / plan_image (host_plan.hip).
  */
 #include "wtp_host.h"
@@ -114,6 +114,42 @@ static void abs_tiny_launches(const wtp_tensor* tensors, int ntensors, const Abs
         if (t == ntensors || a.path[t] != WTP_ABS_PATH_TINY) continue;
         const TPlan& p = a.ps[t];
         tiny_append(tab, tensors[t].in, tensors[t].out, p.B, p.H, p.W, p.L, a.nl_log2[t]).res = t;
+    }
+}
+
+/* the sweep's tiny-image tensors, ABS_SWEEP_MAX_SEG per launch: the segment of tensor t carries
+ * its output at every threshold */
+static void abs_tiny_sweep_launches(const wtp_tensor* tensors, int ntensors, const AbsPlan& a, const Taps& tp,
+                                    const AbsThr& thr, float* const* outs, wtp_abs_result* results, hipStream_t s) {
+    AbsSweepTable tab;
+    auto reset = [&]() {
+        memset(&tab, 0, offsetof(AbsSweepTable, tp));
+        tab.ntensors = ntensors;
+        tab.thr = thr;
+    };
+    reset();
+    tab.tp = tp;
+    for (int t = 0; t <= ntensors; ++t) {
+        const bool flush = t == ntensors || (tab.nseg == ABS_SWEEP_MAX_SEG) ||
+                           (t < ntensors && a.path[t] == WTP_ABS_PATH_TINY &&
+                            (int64_t)tab.nwave + tiny_waves(a.ps[t].B, a.nl_log2[t]) > (int64_t)INT32_MAX);
+        if (flush && tab.nseg) {
+            launch_abs_tiny_sweep(tab, results, s);
+            reset();
+        }
+        if (t == ntensors || a.path[t] != WTP_ABS_PATH_TINY) continue;
+        const TPlan& p = a.ps[t];
+        AbsSweepSeg& sg = tab.s[tab.nseg];
+        sg.in = tensors[t].in;
+        for (int k = 0; k < thr.n; ++k) sg.out[k] = outs[(size_t)k * ntensors + t];
+        sg.B = (int32_t)p.B;
+        sg.H = (uint8_t)p.H;
+        sg.W = (uint8_t)p.W;
+        sg.L = (uint8_t)p.L;
+        sg.nl_log2 = (uint8_t)a.nl_log2[t];
+        sg.res = t;
+        tab.wave_begin[tab.nseg++] = tab.nwave;
+        tab.nwave += (int32_t)tiny_waves(p.B, a.nl_log2[t]);
     }
 }
 
@@ -339,6 +375,104 @@ int wtp_prune_abs_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, i
         }
         launch_abs_count(tensors[t].out, p.numel, reinterpret_cast<unsigned long long*>(&results[t].nonzero_out),
                          nullptr, init, s);
+    }
+    return check_launch();
+}
+
+/* ---- the absolute-threshold sweep: one forward per tensor, every threshold's mask and inverse.
+ * plan_abs's plan and workspace; the line at its start holds a float32 word per threshold. ---- */
+size_t wtp_abs_sweep_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int nthr) {
+    if (ntensors < 0 || (ntensors > 0 && !tensors) || nthr < 1 || nthr > WTP_ABS_SWEEP_MAX_THR) return 0;
+    AbsPlan a;
+    if (plan_abs(tensors, ntensors, wavelet_id, level, false, a) != WTP_OK) return 0;
+    return a.total;
+}
+
+int wtp_prune_abs_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, const double* thresholds,
+                            int nthr, float* const* outs, void* ws, size_t ws_bytes, wtp_abs_result* results,
+                            wtp_stream_t stream) {
+    static_assert(WTP_ABS_SWEEP_MAX_THR == ABS_SWEEP_MAX_THR && ABS_SWEEP_MAX_THR * sizeof(float) <= ALIGN,
+                  "the threshold words fit the workspace's first line");
+    clear_error();
+    if (ntensors < 0 || (ntensors > 0 && (!tensors || !results))) return fail(WTP_EARG, -1, "bad arguments");
+    if (nthr < 1 || nthr > WTP_ABS_SWEEP_MAX_THR || !thresholds)
+        return fail(WTP_EARG, -1, "a sweep takes 1 to %d thresholds", WTP_ABS_SWEEP_MAX_THR);
+    if (ntensors == 0) return WTP_OK;
+    const int n = ntensors;
+    /* the outputs are outs': the plan reads shapes and inputs only (tensors[t].out is ignored) */
+    std::vector<wtp_tensor> ts(tensors, tensors + n);
+    for (auto& x : ts) x.out = const_cast<float*>(x.in);
+    AbsPlan a;
+    int rc = plan_abs(ts.data(), n, wavelet_id, level, true, a);
+    if (rc != WTP_OK) return rc;
+    bool any_live = false;
+    for (int t = 0; t < n; ++t) any_live = any_live || a.ps[t].numel > 0;
+    if (any_live && !outs) return fail(WTP_EARG, -1, "outs is NULL");
+    for (int t = 0; t < n; ++t) {
+        if (a.ps[t].numel == 0) continue;
+        for (int k = 0; k < nthr; ++k) {
+            if (!outs[(size_t)k * n + t]) return fail(WTP_EARG, t, "tensor %d: output %d is a null pointer", t, k);
+            for (int j = 0; j < k; ++j)
+                if (outs[(size_t)j * n + t] == outs[(size_t)k * n + t])
+                    return fail(WTP_EARG, t, "tensor %d: outputs %d and %d are the same buffer", t, j, k);
+        }
+    }
+    if (!ws || ws_bytes < a.total)
+        return fail(WTP_EWORKSPACE, -1, "workspace too small: need %zu bytes, got %zu", a.total, ws_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const Taps tp = taps_for(wavelet_id);
+    AbsThr thr;
+    memset(&thr, 0, sizeof thr);
+    thr.n = nthr;
+    for (int k = 0; k < nthr; ++k) {
+        const float t32 = (float)thresholds[k]; /* the float32 compare of wtp_prune_abs_f32 */
+        memcpy(&thr.bits[k], &t32, 4);
+    }
+    float* thr_dev = reinterpret_cast<float*>(ws);
+    bool any_other = false;
+    for (int t = 0; t < n; ++t) any_other = any_other || (a.path[t] != WTP_ABS_PATH_TINY && a.ps[t].numel > 0);
+    launch_abs_sweep_init(results, nthr * n, any_other ? thr_dev : nullptr, thr, s);
+    /* 1. every tiny-image tensor: read and taken forward once, all thresholds in the launch */
+    abs_tiny_sweep_launches(tensors, n, a, tp, thr, outs, results, s);
+    /* 2. the others, one after another: count_nonzero(in) and (chain) the forward transform once,
+     * before any output is written; then per threshold the mask or the inverse with that
+     * threshold's word on the load, and count_nonzero of that output.  An output that is the
+     * input goes last: the mask reads the input for every threshold. */
+    float* P = wsb<float>(ws, ALIGN);
+    for (int t = 0; t < n; ++t) {
+        const TPlan& p = a.ps[t];
+        if (a.path[t] == WTP_ABS_PATH_TINY || p.numel == 0) continue;
+        wtp_abs_result init;
+        memset(&init, 0, sizeof init);
+        init.numel = p.numel;
+        init.coeff_numel = p.pop;
+        init.level = p.ndim >= 2 ? p.L : 0;
+        init.path = a.path[t];
+        launch_abs_count_sweep(tensors[t].in, p.numel, results + t, n, thr, init, s);
+        std::vector<Chain> fwd;
+        if (a.path[t] == WTP_ABS_PATH_CHAIN) {
+            if (!p.tight) launch_abs_zero(P, p.pop, s);
+            fwd.push_back(make_chain(p, tensors[t].in, nullptr, P, wsb(ws, ALIGN + a.p_bytes), a.t_bytes, nullptr, nullptr));
+            forward_chains(fwd, tp, s);
+        }
+        int order[WTP_ABS_SWEEP_MAX_THR], no = 0;
+        for (int k = 0; k < nthr; ++k)
+            if (outs[(size_t)k * n + t] != tensors[t].in) order[no++] = k;
+        for (int k = 0; k < nthr; ++k)
+            if (outs[(size_t)k * n + t] == tensors[t].in) order[no++] = k;
+        for (int i = 0; i < nthr; ++i) {
+            const int k = order[i];
+            const size_t ri = (size_t)k * n + t;
+            if (a.path[t] == WTP_ABS_PATH_MASK) {
+                launch_copy_threshold(tensors[t].in, outs[ri], p.numel, thr_dev + k, nullptr, s);
+            } else {
+                const std::vector<Chain> inv{make_chain(p, tensors[t].in, outs[ri], P, wsb(ws, ALIGN + a.p_bytes), a.t_bytes,
+                                                        thr_dev + k, nullptr)};
+                inverse_chains(inv, tp, s);
+            }
+            launch_abs_count(outs[ri], p.numel, reinterpret_cast<unsigned long long*>(&results[ri].nonzero_out), nullptr,
+                             init, s);
+        }
     }
     return check_launch();
 }

@@ -486,6 +486,44 @@ void launch_abs_zero(float* p, int64_t n, hipStream_t s);
 void launch_abs_tiny(const AbsTable& t, wtp_abs_result* res, hipStream_t s);
 void launch_abs_count(const float* x, int64_t n, unsigned long long* dst, wtp_abs_result* rec,
                       const wtp_abs_result& init, hipStream_t s);
+/* ---- the absolute-threshold sweep (abs.hip, wtp_prune_abs_sweep_f32) ----
+ * k_abs_tiny_sweep: k_abs_tiny's wave, lane and arena scheme; a wave reads its images once, runs
+ * the forward once and then every threshold's inverse over the raw coefficients it kept in LDS
+ * (wt_abs_sweep_core.h).  A segment carries an output per threshold, so a launch takes fewer
+ * tensors than ABS_MAX_SEG.  Records are threshold-major: tensor t at threshold k is record
+ * k * ntensors + t. */
+constexpr int ABS_SWEEP_MAX_THR = 8;   /* = WTP_ABS_SWEEP_MAX_THR */
+constexpr int ABS_SWEEP_MAX_SEG = 24;  /* tensors per k_abs_tiny_sweep launch */
+struct AbsSweepSeg {
+    const float* in;
+    float* out[ABS_SWEEP_MAX_THR];
+    int32_t B;                 /* images */
+    uint8_t H, W, L, nl_log2;
+    int32_t res;               /* record index at threshold 0 */
+    int32_t pad;
+};
+struct AbsThr { /* float32(thresholds[k]), k < n */
+    int32_t n;
+    int32_t pad;
+    uint32_t bits[ABS_SWEEP_MAX_THR];
+};
+struct AbsSweepTable {
+    int32_t nseg, nwave;
+    int32_t ntensors;          /* the record stride between thresholds */
+    int32_t pad;
+    AbsThr thr;
+    int32_t wave_begin[ABS_SWEEP_MAX_SEG];
+    AbsSweepSeg s[ABS_SWEEP_MAX_SEG];
+    Taps tp;
+};
+static_assert(sizeof(AbsSweepTable) + 8 <= 4096, "k_abs_tiny_sweep's kernel argument");
+/* the call's first launch: every record zero, threshold word k at thr_words[k] */
+void launch_abs_sweep_init(wtp_abs_result* res, int n, float* thr_words, const AbsThr& thr, hipStream_t s);
+void launch_abs_tiny_sweep(const AbsSweepTable& t, wtp_abs_result* res, hipStream_t s);
+/* count_nonzero(x) once, added to nonzero_in of the tensor's thr.n records (rec, rec + stride,
+ * ...), each of which also gets its fixed fields (init's, with its own threshold) */
+void launch_abs_count_sweep(const float* x, int64_t n, wtp_abs_result* rec, int64_t stride, const AbsThr& thr,
+                            const wtp_abs_result& init, hipStream_t s);
 /* ---- the extension modes (modes.hip; arithmetic and geometry: wt_modes_core.h) ----
  * one level of one tensor, per-point: the two analysis passes through tL / tH, the two synthesis
  * passes through tL / tH (the level's output cropped to oH x oW) */

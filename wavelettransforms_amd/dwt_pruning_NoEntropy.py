@@ -5,6 +5,7 @@ Same public names, arguments, return values and printed lines as the reference m
 arithmetic runs in libwtprune.so (HIP, gfx950; wtp_prune_abs_f32) on device-resident tensors:
 
   multi_resolution_analysis    dwt_pruning_NoEntropy.py:12-62
+  multi_resolution_analysis_sweep   the same at a grid of thresholds, one device call (an addition)
   prune_layer_weights          dwt_pruning_NoEntropy.py:65-91
   wavelet_pruning              dwt_pruning_NoEntropy.py:94-138
 
@@ -33,7 +34,7 @@ from . import _native as N
 from .utils import (append_to_experiment_log, check_and_set_pruned_instance_path, log_pruning_details,
                     save_model, setup_csv_writer)
 
-__all__ = ["multi_resolution_analysis", "prune_layer_weights", "wavelet_pruning"]
+__all__ = ["multi_resolution_analysis", "multi_resolution_analysis_sweep", "prune_layer_weights", "wavelet_pruning"]
 
 
 def _cuda(x):
@@ -79,6 +80,32 @@ def multi_resolution_analysis(weights: List[torch.Tensor], wavelet: str, level: 
         return [], 0
     outs, recs = _run(weights, wavelet, level, threshold)
     return outs, int(sum(r["nonzero_in"] - r["nonzero_out"] for r in recs))
+
+
+def multi_resolution_analysis_sweep(weights: List[torch.Tensor], wavelet: str, level: int,
+                                    thresholds) -> List[Tuple[List[torch.Tensor], int]]:
+    """multi_resolution_analysis at several thresholds in one device call (the reference's
+    experiment runs the same model and wavelet at a grid of thresholds).  Returns a list over
+    `thresholds` of (pruned tensors, total pruned count), each entry what
+    multi_resolution_analysis(weights, wavelet, level, thresholds[k]) returns; every tensor is read
+    and transformed forward once for all of them (engine.prune_abs_sweep; at most
+    engine.WTP_ABS_SWEEP_MAX_THR thresholds a call, longer grids run in several).  The level
+    warning is raised as multi_resolution_analysis raises it."""
+    thresholds = list(thresholds)
+    weights = list(weights)
+    if len(weights) == 0:
+        return [([], 0) for _ in thresholds]
+    _warn_levels(weights, wavelet, level)
+    result = []
+    with torch.no_grad():
+        devs = [w.device for w in weights]
+        dev_w = [_cuda(w.detach()) for w in weights]
+        for i in range(0, len(thresholds), engine.WTP_ABS_SWEEP_MAX_THR):
+            outs, recs = engine.prune_abs_sweep(dev_w, wavelet, level, thresholds[i:i + engine.WTP_ABS_SWEEP_MAX_THR])
+            for o, r in zip(outs, recs):
+                pruned = [y.to(d).to(dtype=w.dtype).view(w.shape) for y, d, w in zip(o, devs, weights)]
+                result.append((pruned, int(sum(x["nonzero_in"] - x["nonzero_out"] for x in r))))
+    return result
 
 
 def _copy_back(params, pruned):

@@ -31,7 +31,7 @@ def workspace(device, nbytes, stream=None, kind=None):
     ever used keeps its workspace (at the largest size it needed: a cfg5-sized call holds the
     packed coefficients of its images) until release_workspaces() drops it.  kind=None is the
     workspace of the selection entries, whose state the library keeps clean; an entry that uses its
-    workspace as plain scratch (launch_abs: kind="abs", launch_sweep: kind="sweep") gets one of its
+    workspace as plain scratch (launch_abs and launch_abs_sweep: kind="abs", launch_sweep: kind="sweep") gets one of its
     own, so it never writes over that state."""
     device = torch.device(device)
     if device.index is None:
@@ -403,6 +403,64 @@ def prune_abs(tensors, wavelet, level, threshold, outs=None):
     if res is None:
         return outs, []
     return outs, decode_abs(res, len(tensors))
+
+
+WTP_ABS_SWEEP_MAX_THR = 8  # include/wtprune.h
+
+
+def launch_abs_sweep(tensors, wavelet, level, thresholds, outs=None, stream=None):
+    """Enqueue the absolute-threshold sweep (wtp_prune_abs_sweep_f32) for `tensors` (CUDA float32) on
+    `stream` (default: the current stream): every tensor is read and transformed forward once,
+    then each threshold's mask and inverse writes its output.  Returns (outs, results_dev) without
+    synchronising: outs[k][t] is tensor t pruned at thresholds[k], bit for bit what
+    launch_abs(tensors, wavelet, level, thresholds[k]) gives, and block k of results_dev
+    (len(tensors) wtp_abs_result records) is that call's records.  At most eight thresholds; they
+    may repeat and need not be sorted.  outs: a list over the thresholds of output lists; at most
+    one output of a tensor may be the tensor itself."""
+    thresholds = [float(v) for v in thresholds]
+    nthr = len(thresholds)
+    check_tensors(tensors)
+    tensors = [x.contiguous() for x in tensors]
+    if outs is None:
+        outs = [[torch.empty_like(x) for x in tensors] for _ in range(nthr)]
+    else:
+        if len(outs) != nthr:
+            raise ValueError("wavelettransforms_amd: %d output sets for %d thresholds" % (len(outs), nthr))
+        for o in outs:
+            check_outs(tensors, o)
+    n = len(tensors)
+    if n == 0:
+        return outs, None
+    device = tensors[0].device
+    L = N.lib()
+    wid = wavelet_id(wavelet)
+    desc = _as_desc(tensors, tensors)
+    if stream is None:
+        stream = torch.cuda.current_stream(device)
+    nbytes = L.wtp_abs_sweep_workspace_size(desc, n, wid, int(level), nthr)
+    # scratch of the absolute-threshold entries alone: never the selection entries' workspace
+    ws = workspace(device, nbytes if nbytes else 256, stream, kind="abs")
+    with torch.cuda.stream(stream):
+        res = torch.empty(max(1, nthr) * n * N.ABS_RESULT_BYTES, dtype=torch.uint8, device=device)
+    tarr = (ctypes.c_double * max(1, nthr))(*thresholds)
+    optr = (ctypes.c_void_p * max(1, nthr * n))(*[y.data_ptr() if y.numel() else None for o in outs for y in o])
+    rc = L.wtp_prune_abs_sweep_f32(desc, n, wid, int(level), tarr, nthr, optr, ws.data_ptr(), ws.numel(),
+                                   res.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    if rc != N.WTP_OK:
+        raise_for(rc, tensors, wavelet)
+    return outs, res
+
+
+def prune_abs_sweep(tensors, wavelet, level, thresholds, outs=None):
+    """launch_abs_sweep() + wait + decoded records: (outs, recs) with recs[k][t] the record of
+    tensor t at thresholds[k] (decode_abs() of block k)."""
+    thresholds = list(thresholds)
+    outs, res = launch_abs_sweep(tensors, wavelet, level, thresholds, outs=outs)
+    nthr, n = len(thresholds), len(tensors)
+    if res is None:
+        return outs, [[] for _ in range(nthr)]
+    blocks = res.view(nthr, n * N.ABS_RESULT_BYTES)
+    return outs, [decode_abs(blocks[k], n) for k in range(nthr)]
 
 
 WTP_SWEEP_MAX_PCT, WTP_SWEEP_THRESHOLDS_ONLY, MODE_SWEEP = 8, 16, 5  # include/wtprune.h
