@@ -38,7 +38,9 @@ def test_symbols_exported_and_declared():
     assert N.RESULT_BYTES == 48  # wtp_result's layout is unchanged
 
 
-@pytest.mark.parametrize("shapes,wavelet,level,code", [
+# (shapes, wavelet, level, status or None for a valid request); the sweep entry takes the same rows
+# (tests/test_abs_sweep_host.py)
+ABS_TABLE = [
     ([(4, 4, 3, 3)], "nosuch", 1, N.WTP_EBADWAVELET),
     ([(16,)], "nosuch", 1, None),                          # ndim < 2 never looks the wavelet up
     ([(16,)], "haar", -1, None),                           # ... nor the level
@@ -51,7 +53,10 @@ def test_symbols_exported_and_declared():
     ([(2, 2, 2, 18, 33)], "db2", 1, None),
     ([(4, 4, 3, 3)], "bior3.3", 5, None),                  # above dwt_max_level: not clamped, not an error
     ([(16,), (33, 17), (0, 5)], "db4", 2, N.WTP_EARG),     # the third tensor fails, index reported
-])
+]
+
+
+@pytest.mark.parametrize("shapes,wavelet,level,code", ABS_TABLE)
 def test_validation_before_any_device_work(shapes, wavelet, level, code):
     L = N.lib()
     wid = L.wtp_wavelet_id(wavelet.encode())

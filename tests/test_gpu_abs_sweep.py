@@ -148,6 +148,51 @@ def test_chain_and_limit_shapes(eng, shape, wavelet, level, path):
         assert r["coeff_numel"] == x.size // (shape[-2] * shape[-1]) * pr * pc
 
 
+# every branch of the body the two entries share: tiny (the second is more than a wave of images,
+# its last wave partial), a 1-D mask, an empty tensor; a level-0 mask; a chain that is not tight; a chain
+ONE_THRESHOLD_LISTS = [
+    ("bior3.3", 5, [(5, 3, 3, 3), (70, 1, 1, 1), (64,), (0,)], [TINY, TINY, MASK, None]),
+    ("haar", 0, [(3, 2, 9, 9)], [MASK]),
+    ("db4", 2, [(33, 17)], [CHAIN]),
+    ("db8", 3, [(64, 8)], [CHAIN]),
+]
+
+
+def test_one_threshold_sweep_equals_the_ordinary_call(eng):
+    """A sweep of one threshold and the ordinary call issue the same launches but for the tiny
+    kernel: outputs equal by bits, records field for field, out of place and with the inputs as
+    the outputs.  The threshold is 0.6745 x the list's sigma."""
+    for wavelet, level, shapes, paths in ONE_THRESHOLD_LISTS:
+        sigma = G.W.conv_sigma(shapes[0]) if len(shapes[0]) == 4 else 1.0 / math.sqrt(shapes[0][-1])
+        xs_np = [G.W.synth_numpy(s, 79, i, G.W.sigma_exponent(sigma)) for i, s in enumerate(shapes)]
+        thr = 0.6745 * sigma
+        for x in xs_np:  # a guard of the test's own inputs, on the oracle alone: the case is not trivial
+            if x.size:
+                c = O.wavedec2_packed(x, wavelet, level) if x.ndim >= 2 else x
+                assert 0.0 < float((np.abs(c) < np.float32(thr)).mean()) < 1.0, x.shape
+        runs = []
+        for in_place in (False, True):
+            xs, ys = _cuda(xs_np), _cuda(xs_np)
+            outs_s, recs_s = eng.prune_abs_sweep(xs, wavelet, level, [thr], outs=[xs] if in_place else None)
+            outs_1, recs_1 = eng.prune_abs(ys, wavelet, level, thr, outs=ys if in_place else None)
+            assert len(outs_s) == len(recs_s) == 1
+            if in_place:
+                assert all(a is b for a, b in zip(outs_s[0], xs)) and all(a is b for a, b in zip(outs_1, ys))
+            for x, a, b, ra, rb, path in zip(xs_np, outs_s[0], outs_1, recs_s[0], recs_1, paths):
+                tag = (wavelet, level, x.shape, in_place)
+                _same(a.cpu().numpy(), b.cpu().numpy(), tag)
+                assert _rec_equal(ra, rb), (tag, ra, rb)
+                if x.size == 0:  # an empty tensor's record stays zero
+                    assert not any(ra.values()), (tag, ra)
+                    continue
+                assert ra["path"] == path and ra["thr32_bits"] == G.f32_bits(thr), (tag, ra)
+                assert ra["numel"] == x.size and ra["nonzero_in"] == int(np.count_nonzero(x)), (tag, ra)
+            runs.append(([o.cpu().numpy() for o in outs_s[0]], recs_s[0]))
+        for a, b in zip(runs[0][0], runs[1][0]):  # in place gives what out of place gives
+            _same(a, b, (wavelet, level, a.shape))
+        assert runs[0][1] == runs[1][1]
+
+
 def test_more_tensors_than_a_launch_table(eng):
     """The 150-tensor list of test_more_tiny_tensors_than_one_launch_table (1-D and chain tensors
     between the tiny ones): several k_abs_tiny_sweep launches, whose wave numbering restarts while

@@ -21,7 +21,8 @@ static void launch_tiny_chains(const std::vector<Chain>& cs, const Taps& tp, hip
     for (const Chain& c : cs) {
         const TPlan& p = *c.p;
         if (p.tiny_lg < 0) continue;
-        MTinySeg& sg = tiny_append(tab, c.in, c.out, p.B, p.H, p.W, p.L, p.tiny_lg);
+        MTinySeg& sg = tiny_append(tab, c.in, p.B, p.H, p.W, p.L, p.tiny_lg);
+        sg.out = c.out;
         sg.P = c.P;
         sg.thr = c.thr;
         sg.zc = c.zc;

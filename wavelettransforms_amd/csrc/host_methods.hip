@@ -3,6 +3,8 @@
  * the sparsity count, the absolute-threshold method and its sweep, the transform components and the synthetic
  * inputs.  Each validates with its own rules on top of read_shape / plan_image (host_plan.hip).
  */
+#include <type_traits>
+
 #include "wtp_host.h"
 #include "wt_perm.h"
 
@@ -92,65 +94,114 @@ static int plan_abs(const wtp_tensor* ts, int n, int wid, int level, bool check_
     return WTP_OK;
 }
 
-/* every tiny-image tensor of the call, ABS_MAX_SEG tensors per launch (the table is the kernel's
- * argument) */
-static void abs_tiny_launches(const wtp_tensor* tensors, int ntensors, const AbsPlan& a, const Taps& tp, uint32_t thr_bits,
-                              wtp_abs_result* results, hipStream_t s) {
-    AbsTable tab;
-    auto reset = [&]() {
-        memset(&tab, 0, offsetof(AbsTable, tp));
-        tab.thr_bits = thr_bits;
-    };
-    reset();
-    tab.tp = tp;
+/* np.abs(a_f32) < python_float compares in float32 with the threshold rounded to float32 */
+static AbsThr abs_thr(const double* thresholds, int nthr) {
+    AbsThr thr;
+    memset(&thr, 0, sizeof thr);
+    thr.n = nthr;
+    for (int k = 0; k < nthr; ++k) {
+        const float t32 = (float)thresholds[k];
+        memcpy(&thr.bits[k], &t32, 4);
+    }
+    return thr;
+}
+
+/* Every tiny-image tensor of the call, as many per launch as the table -- the kernel's argument --
+ * has segments (AbsTable: ABS_MAX_SEG, AbsSweepTable: ABS_SWEEP_MAX_SEG).  `head` is a table without
+ * segments, its call-wide fields set; set_out(sg, t) gives tensor t's segment its output(s). */
+template <class Table, class SetOut>
+static void abs_tiny_launches(const Table& head, const wtp_tensor* tensors, int ntensors, const AbsPlan& a,
+                              const SetOut& set_out, wtp_abs_result* results, hipStream_t s) {
+    constexpr int max_seg = (int)std::extent<decltype(Table::s)>::value;
+    Table tab = head;
     for (int t = 0; t <= ntensors; ++t) {
-        const bool flush = t == ntensors || (tab.nseg == ABS_MAX_SEG) ||
-                           (t < ntensors && a.path[t] == WTP_ABS_PATH_TINY &&
-                            (int64_t)tab.nwave + tiny_waves(a.ps[t].B, a.nl_log2[t]) > (int64_t)INT32_MAX);
+        const bool tiny = t < ntensors && a.path[t] == WTP_ABS_PATH_TINY;
+        const bool flush = t == ntensors || tab.nseg == max_seg ||
+                           (tiny && (int64_t)tab.nwave + tiny_waves(a.ps[t].B, a.nl_log2[t]) > (int64_t)INT32_MAX);
         if (flush && tab.nseg) {
             launch_abs_tiny(tab, results, s);
-            reset();
+            tab = head;
         }
-        if (t == ntensors || a.path[t] != WTP_ABS_PATH_TINY) continue;
+        if (!tiny) continue;
         const TPlan& p = a.ps[t];
-        tiny_append(tab, tensors[t].in, tensors[t].out, p.B, p.H, p.W, p.L, a.nl_log2[t]).res = t;
+        auto& sg = tiny_append(tab, tensors[t].in, p.B, p.H, p.W, p.L, a.nl_log2[t]);
+        sg.res = t;
+        set_out(sg, t);
     }
 }
 
-/* the sweep's tiny-image tensors, ABS_SWEEP_MAX_SEG per launch: the segment of tensor t carries
- * its output at every threshold */
-static void abs_tiny_sweep_launches(const wtp_tensor* tensors, int ntensors, const AbsPlan& a, const Taps& tp,
-                                    const AbsThr& thr, float* const* outs, wtp_abs_result* results, hipStream_t s) {
-    AbsSweepTable tab;
-    auto reset = [&]() {
-        memset(&tab, 0, offsetof(AbsSweepTable, tp));
-        tab.ntensors = ntensors;
-        tab.thr = thr;
-    };
-    reset();
-    tab.tp = tp;
-    for (int t = 0; t <= ntensors; ++t) {
-        const bool flush = t == ntensors || (tab.nseg == ABS_SWEEP_MAX_SEG) ||
-                           (t < ntensors && a.path[t] == WTP_ABS_PATH_TINY &&
-                            (int64_t)tab.nwave + tiny_waves(a.ps[t].B, a.nl_log2[t]) > (int64_t)INT32_MAX);
-        if (flush && tab.nseg) {
-            launch_abs_tiny_sweep(tab, results, s);
-            reset();
-        }
-        if (t == ntensors || a.path[t] != WTP_ABS_PATH_TINY) continue;
-        const TPlan& p = a.ps[t];
-        AbsSweepSeg& sg = tab.s[tab.nseg];
-        sg.in = tensors[t].in;
-        for (int k = 0; k < thr.n; ++k) sg.out[k] = outs[(size_t)k * ntensors + t];
-        sg.B = (int32_t)p.B;
-        sg.H = (uint8_t)p.H;
-        sg.W = (uint8_t)p.W;
-        sg.L = (uint8_t)p.L;
-        sg.nl_log2 = (uint8_t)a.nl_log2[t];
-        sg.res = t;
-        tab.wave_begin[tab.nseg++] = tab.nwave;
-        tab.nwave += (int32_t)tiny_waves(p.B, a.nl_log2[t]);
+/* The launch sequence of both absolute-threshold entries: thr.n thresholds, tensor t's output at
+ * threshold k in outs[k * n + t] and its record in results[k * n + t].  `sweep` picks the tiny
+ * kernel and nothing else: k_abs_tiny_sweep whatever thr.n is, or k_abs_tiny (thr.n == 1), which
+ * is the faster of the two for one threshold. */
+static int abs_run(const wtp_tensor* tensors, int n, const AbsPlan& a, const Taps& tp, const AbsThr& thr,
+                   float* const* outs, bool sweep, void* ws, wtp_abs_result* results, hipStream_t s) {
+    static_assert(WTP_ABS_SWEEP_MAX_THR == ABS_SWEEP_MAX_THR && ABS_SWEEP_MAX_THR * sizeof(float) <= ALIGN,
+                  "the threshold words fit the workspace's first line");
+    float* thr_dev = reinterpret_cast<float*>(ws);
+    bool any_other = false;
+    for (int t = 0; t < n; ++t) any_other = any_other || (a.path[t] != WTP_ABS_PATH_TINY && a.ps[t].numel > 0);
+    /* the counts are accumulated: every record starts from zero (an empty tensor's stays so); the
+     * mask and the inverse read their threshold from device memory: the same launch sets the words */
+    launch_abs_init(results, thr.n * n, any_other ? thr_dev : nullptr, thr, s);
+    /* 1. every tiny-image tensor: read, taken forward and counted once, all thresholds in the launch */
+    if (sweep) {
+        AbsSweepTable head;
+        memset(&head, 0, sizeof head);
+        head.ntensors = n;
+        head.thr = thr;
+        head.tp = tp;
+        abs_tiny_launches(head, tensors, n, a, [&](AbsSweepSeg& sg, int t) {
+            for (int k = 0; k < thr.n; ++k) sg.out[k] = outs[(size_t)k * n + t];
+        }, results, s);
+    } else {
+        AbsTable head;
+        memset(&head, 0, sizeof head);
+        head.thr_bits = thr.bits[0];
+        head.tp = tp;
+        abs_tiny_launches(head, tensors, n, a, [&](AbsSeg& sg, int t) { sg.out = outs[t]; }, results, s);
     }
+    /* 2. the others, one after another: count_nonzero(in) and (chain) the forward transform once,
+     * before any output is written; then per threshold the mask or the inverse with that
+     * threshold's word on the load, and count_nonzero of that output.  An output that is the
+     * input goes last: the mask reads the input for every threshold. */
+    float* P = wsb<float>(ws, ALIGN);
+    for (int t = 0; t < n; ++t) {
+        const TPlan& p = a.ps[t];
+        if (a.path[t] == WTP_ABS_PATH_TINY || p.numel == 0) continue;
+        const bool chain = a.path[t] == WTP_ABS_PATH_CHAIN;
+        wtp_abs_result init;
+        memset(&init, 0, sizeof init);
+        init.numel = p.numel;
+        init.coeff_numel = p.pop;
+        init.level = p.ndim >= 2 ? p.L : 0;
+        init.path = a.path[t];
+        launch_abs_count_in(tensors[t].in, p.numel, results + t, n, thr, init, s);
+        /* one chain: the forward reads its `in`, each inverse its `out` and `thr` */
+        Chain c = make_chain(p, tensors[t].in, nullptr, P, wsb(ws, ALIGN + a.p_bytes), a.t_bytes, nullptr, nullptr);
+        if (chain) {
+            if (!p.tight) launch_abs_zero(P, p.pop, s);
+            forward_chains({c}, tp, s);
+        }
+        int order[WTP_ABS_SWEEP_MAX_THR], no = 0;
+        for (int k = 0; k < thr.n; ++k)
+            if (outs[(size_t)k * n + t] != tensors[t].in) order[no++] = k;
+        for (int k = 0; k < thr.n; ++k)
+            if (outs[(size_t)k * n + t] == tensors[t].in) order[no++] = k;
+        for (int i = 0; i < thr.n; ++i) {
+            const int k = order[i];
+            const size_t ri = (size_t)k * n + t;
+            if (chain) {
+                c.out = outs[ri];
+                c.thr = thr_dev + k;
+                inverse_chains({c}, tp, s);
+            } else {
+                launch_copy_threshold(tensors[t].in, outs[ri], p.numel, thr_dev + k, nullptr, s);
+            }
+            launch_abs_count(outs[ri], p.numel, reinterpret_cast<unsigned long long*>(&results[ri].nonzero_out), s);
+        }
+    }
+    return check_launch();
 }
 
 /* ---------------------------------------------------------- components --- */
@@ -335,48 +386,10 @@ int wtp_prune_abs_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, i
     if (rc != WTP_OK) return rc;
     if (!ws || ws_bytes < a.total)
         return fail(WTP_EWORKSPACE, -1, "workspace too small: need %zu bytes, got %zu", a.total, ws_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    const Taps tp = taps_for(wavelet_id);
-    /* np.abs(a_f32) < python_float compares in float32 with the threshold rounded to float32 */
-    const float thr32 = (float)threshold;
-    uint32_t thr_bits;
-    memcpy(&thr_bits, &thr32, 4);
-    float* thr_dev = reinterpret_cast<float*>(ws);
-    bool any_other = false;
-    for (int t = 0; t < ntensors; ++t) any_other = any_other || (a.path[t] != WTP_ABS_PATH_TINY && a.ps[t].numel > 0);
-    /* the counts are accumulated: every record starts from zero (an empty tensor's stays so); the
-     * existing kernels read the threshold from device memory: the same launch sets that word */
-    launch_abs_init(results, ntensors, any_other ? thr_dev : nullptr, thr_bits, s);
-    /* 1. every tiny-image tensor of the call in one launch */
-    abs_tiny_launches(tensors, ntensors, a, tp, thr_bits, results, s);
-    /* 2. the others, one after another: count_nonzero(in) before out is written (in place),
-     * the transform or the plain mask, count_nonzero(out) */
-    float* P = wsb<float>(ws, ALIGN);
-    for (int t = 0; t < ntensors; ++t) {
-        const TPlan& p = a.ps[t];
-        if (a.path[t] == WTP_ABS_PATH_TINY || p.numel == 0) continue;
-        wtp_abs_result init;
-        memset(&init, 0, sizeof init);
-        init.numel = p.numel;
-        init.coeff_numel = p.pop;
-        init.thr32_bits = thr_bits;
-        init.level = p.ndim >= 2 ? p.L : 0;
-        init.path = a.path[t];
-        launch_abs_count(tensors[t].in, p.numel, reinterpret_cast<unsigned long long*>(&results[t].nonzero_in),
-                         results + t, init, s);
-        if (a.path[t] == WTP_ABS_PATH_MASK) {
-            launch_copy_threshold(tensors[t].in, tensors[t].out, p.numel, thr_dev, nullptr, s);
-        } else {
-            if (!p.tight) launch_abs_zero(P, p.pop, s);
-            const std::vector<Chain> cs{make_chain(p, tensors[t].in, tensors[t].out, P, wsb(ws, ALIGN + a.p_bytes),
-                                                   a.t_bytes, thr_dev, nullptr)};
-            forward_chains(cs, tp, s);
-            inverse_chains(cs, tp, s);
-        }
-        launch_abs_count(tensors[t].out, p.numel, reinterpret_cast<unsigned long long*>(&results[t].nonzero_out),
-                         nullptr, init, s);
-    }
-    return check_launch();
+    std::vector<float*> outs(ntensors);
+    for (int t = 0; t < ntensors; ++t) outs[t] = tensors[t].out;
+    return abs_run(tensors, ntensors, a, taps_for(wavelet_id), abs_thr(&threshold, 1), outs.data(), false, ws, results,
+                   (hipStream_t)stream);
 }
 
 /* ---- the absolute-threshold sweep: one forward per tensor, every threshold's mask and inverse.
@@ -391,8 +404,6 @@ size_t wtp_abs_sweep_workspace_size(const wtp_tensor* tensors, int ntensors, int
 int wtp_prune_abs_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, const double* thresholds,
                             int nthr, float* const* outs, void* ws, size_t ws_bytes, wtp_abs_result* results,
                             wtp_stream_t stream) {
-    static_assert(WTP_ABS_SWEEP_MAX_THR == ABS_SWEEP_MAX_THR && ABS_SWEEP_MAX_THR * sizeof(float) <= ALIGN,
-                  "the threshold words fit the workspace's first line");
     clear_error();
     if (ntensors < 0 || (ntensors > 0 && (!tensors || !results))) return fail(WTP_EARG, -1, "bad arguments");
     if (nthr < 1 || nthr > WTP_ABS_SWEEP_MAX_THR || !thresholds)
@@ -410,71 +421,13 @@ int wtp_prune_abs_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet
     if (any_live && !outs) return fail(WTP_EARG, -1, "outs is NULL");
     for (int t = 0; t < n; ++t) {
         if (a.ps[t].numel == 0) continue;
-        for (int k = 0; k < nthr; ++k) {
-            if (!outs[(size_t)k * n + t]) return fail(WTP_EARG, t, "tensor %d: output %d is a null pointer", t, k);
-            for (int j = 0; j < k; ++j)
-                if (outs[(size_t)j * n + t] == outs[(size_t)k * n + t])
-                    return fail(WTP_EARG, t, "tensor %d: outputs %d and %d are the same buffer", t, j, k);
-        }
+        rc = check_sweep_outs(outs, nthr, n, t);
+        if (rc != WTP_OK) return rc;
     }
     if (!ws || ws_bytes < a.total)
         return fail(WTP_EWORKSPACE, -1, "workspace too small: need %zu bytes, got %zu", a.total, ws_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    const Taps tp = taps_for(wavelet_id);
-    AbsThr thr;
-    memset(&thr, 0, sizeof thr);
-    thr.n = nthr;
-    for (int k = 0; k < nthr; ++k) {
-        const float t32 = (float)thresholds[k]; /* the float32 compare of wtp_prune_abs_f32 */
-        memcpy(&thr.bits[k], &t32, 4);
-    }
-    float* thr_dev = reinterpret_cast<float*>(ws);
-    bool any_other = false;
-    for (int t = 0; t < n; ++t) any_other = any_other || (a.path[t] != WTP_ABS_PATH_TINY && a.ps[t].numel > 0);
-    launch_abs_sweep_init(results, nthr * n, any_other ? thr_dev : nullptr, thr, s);
-    /* 1. every tiny-image tensor: read and taken forward once, all thresholds in the launch */
-    abs_tiny_sweep_launches(tensors, n, a, tp, thr, outs, results, s);
-    /* 2. the others, one after another: count_nonzero(in) and (chain) the forward transform once,
-     * before any output is written; then per threshold the mask or the inverse with that
-     * threshold's word on the load, and count_nonzero of that output.  An output that is the
-     * input goes last: the mask reads the input for every threshold. */
-    float* P = wsb<float>(ws, ALIGN);
-    for (int t = 0; t < n; ++t) {
-        const TPlan& p = a.ps[t];
-        if (a.path[t] == WTP_ABS_PATH_TINY || p.numel == 0) continue;
-        wtp_abs_result init;
-        memset(&init, 0, sizeof init);
-        init.numel = p.numel;
-        init.coeff_numel = p.pop;
-        init.level = p.ndim >= 2 ? p.L : 0;
-        init.path = a.path[t];
-        launch_abs_count_sweep(tensors[t].in, p.numel, results + t, n, thr, init, s);
-        std::vector<Chain> fwd;
-        if (a.path[t] == WTP_ABS_PATH_CHAIN) {
-            if (!p.tight) launch_abs_zero(P, p.pop, s);
-            fwd.push_back(make_chain(p, tensors[t].in, nullptr, P, wsb(ws, ALIGN + a.p_bytes), a.t_bytes, nullptr, nullptr));
-            forward_chains(fwd, tp, s);
-        }
-        int order[WTP_ABS_SWEEP_MAX_THR], no = 0;
-        for (int k = 0; k < nthr; ++k)
-            if (outs[(size_t)k * n + t] != tensors[t].in) order[no++] = k;
-        for (int k = 0; k < nthr; ++k)
-            if (outs[(size_t)k * n + t] == tensors[t].in) order[no++] = k;
-        for (int i = 0; i < nthr; ++i) {
-            const int k = order[i];
-            const size_t ri = (size_t)k * n + t;
-            if (a.path[t] == WTP_ABS_PATH_MASK) {
-                launch_copy_threshold(tensors[t].in, outs[ri], p.numel, thr_dev + k, nullptr, s);
-            } else {
-                const std::vector<Chain> inv{make_chain(p, tensors[t].in, outs[ri], P, wsb(ws, ALIGN + a.p_bytes), a.t_bytes,
-                                                        thr_dev + k, nullptr)};
-                inverse_chains(inv, tp, s);
-            }
-            launch_abs_count(outs[ri], p.numel, reinterpret_cast<unsigned long long*>(&results[ri].nonzero_out), nullptr,
-                             init, s);
-        }
-    }
-    return check_launch();
+    return abs_run(tensors, n, a, taps_for(wavelet_id), abs_thr(thresholds, nthr), outs, true, ws, results,
+                   (hipStream_t)stream);
 }
 
 size_t wtp_dwt_workspace_size(int64_t B, int64_t H, int64_t W, int level) {

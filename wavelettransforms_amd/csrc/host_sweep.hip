@@ -97,12 +97,8 @@ int wtp_prune_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id,
     for (int t = 0; t < n; ++t) {
         if (!tensors[t].in) return fail(WTP_EARG, t, "tensor %d: null pointer", t);
         if (thr_only) continue;
-        for (int k = 0; k < npct; ++k) {
-            if (!outs[(size_t)k * n + t]) return fail(WTP_EARG, t, "tensor %d: output %d is a null pointer", t, k);
-            for (int j = 0; j < k; ++j)
-                if (outs[(size_t)j * n + t] == outs[(size_t)k * n + t])
-                    return fail(WTP_EARG, t, "tensor %d: outputs %d and %d are the same buffer", t, j, k);
-        }
+        rc = check_sweep_outs(outs, npct, n, t);
+        if (rc != WTP_OK) return rc;
     }
     if (!ws || ws_bytes < sp.total)
         return fail(WTP_EWORKSPACE, -1, "workspace too small: need %zu bytes, got %zu", sp.total, ws_bytes);

@@ -1,10 +1,11 @@
-/* The wave arena of the tiny-image kernels (k_abs_tiny of abs.hip, k_mtiny_fwd / k_mtiny_inv of
- * modes.hip): a wave, which is a workgroup, takes NL images of one tensor, one image per lane, and
- * keeps word s of image i at arena[s * NL + i], so every LDS access is a wave-uniform offset plus
- * the lane.  The per-image routines (abs_image of wt_abs_core.h, wtm_tiny_fwd / wtm_tiny_inv of
+/* The wave arena of the tiny-image kernels (k_abs_tiny / k_abs_tiny_sweep of abs.hip, k_mtiny_fwd /
+ * k_mtiny_inv of modes.hip): a wave, which is a workgroup, takes NL images of one tensor, one image
+ * per lane, and keeps word s of image i at arena[s * NL + i], so every LDS access is a wave-uniform
+ * offset plus the lane.  The per-image routines (abs_image of wt_abs_core.h, wtm_tiny_fwd / wtm_tiny_inv of
  * wt_modes_core.h) get their image's word 0 and the stride NL; here is what surrounds them.  The
  * arena's size is the caller's (ABS_WAVE_WORDS, WTM_WAVE_WORDS).  The device part serves the two
- * k_mtiny_*; k_abs_tiny measured 0.2 % slower on it and keeps its own text. */
+ * k_mtiny_* and k_abs_tiny_sweep; k_abs_tiny measured 0.2 % slower on it and keeps its own text
+ * (DESIGN.md). */
 #ifndef WT_TINY_ARENA_H
 #define WT_TINY_ARENA_H
 
@@ -35,13 +36,13 @@ WT_CORE void tiny_packed_size(int H, int W, int L, int F, int& PR, int& PC) {
     PC = L ? sC + C : W;
 }
 
-/* The next segment of a launch table (AbsTable, MTinyTable: nseg, nwave, wave_begin[], s[] whose
- * elements begin with in, out, B, H, W, L, nl_log2); the caller fills the rest of it. */
+/* The next segment of a launch table (AbsTable, AbsSweepTable, MTinyTable: nseg, nwave,
+ * wave_begin[], s[] whose elements have in, B, H, W, L, nl_log2); the caller fills the rest of it,
+ * its output or outputs first. */
 template <class Table>
-static inline auto& tiny_append(Table& tab, const float* in, float* out, int64_t B, int64_t H, int64_t W, int L, int lg) {
+static inline auto& tiny_append(Table& tab, const float* in, int64_t B, int64_t H, int64_t W, int L, int lg) {
     auto& sg = tab.s[tab.nseg];
     sg.in = in;
-    sg.out = out;
     sg.B = (int32_t)B;
     sg.H = (uint8_t)H;
     sg.W = (uint8_t)W;

@@ -90,6 +90,19 @@ Layout make_layout(std::vector<TPlan>& ps, const Taps& tp);
 /* the workspace queries: plan (no pointers, percentile 50) and lay out; 0 for an invalid request */
 size_t layout_bytes(const wtp_tensor* ts, int n, int wid, int level, bool carry, bool flat, int mode);
 
+/* The outputs of tensor t of a sweep over n tensors (set-major: set k's at outs[k * n + t]): none
+ * null, no two the same buffer.  Each sweep entry calls it in its tensor loop for the tensors that
+ * need outputs, so its other per-tensor complaints keep their place. */
+inline int check_sweep_outs(float* const* outs, int nsets, int n, int t) {
+    for (int k = 0; k < nsets; ++k) {
+        if (!outs[(size_t)k * n + t]) return fail(WTP_EARG, t, "tensor %d: output %d is a null pointer", t, k);
+        for (int j = 0; j < k; ++j)
+            if (outs[(size_t)j * n + t] == outs[(size_t)k * n + t])
+                return fail(WTP_EARG, t, "tensor %d: outputs %d and %d are the same buffer", t, j, k);
+    }
+    return WTP_OK;
+}
+
 /* ---- segment tables (the percentile path and min pruning) ---- */
 void bucket_plan(int64_t n, int* nsub_log2, int* bucket_cap, bool dwt);
 int64_t cap_for(int64_t n, bool dwt);

@@ -459,8 +459,8 @@ void launch_random_prune(const RandTable& t, wtp_result* res, hipStream_t s);
 void launch_count_small(const float* x, int64_t n, float thr, unsigned long long* count, hipStream_t s);
 /* ---- the absolute-threshold method (abs.hip, wtp_prune_abs_f32) ----
  * k_abs_tiny: one wave (TINY_THREADS) per workgroup and per NL images of one tensor in the arena
- * of wt_tiny_arena.h, whose tiny_append fills what AbsTable and MTinyTable share: nseg, nwave,
- * wave_begin and the head of a segment (in .. nl_log2). */
+ * of wt_tiny_arena.h, whose tiny_append fills what AbsTable, AbsSweepTable and MTinyTable share:
+ * nseg, nwave, wave_begin and a segment's in, B, H, W, L, nl_log2. */
 constexpr int ABS_MAX_SEG = 64;        /* tensors per k_abs_tiny launch (the table is its kernel argument) */
 /* ABS_SIDE_MAX, ABS_TAP_WORDS, ABS_WAVE_WORDS and the lane choice abs_lanes_log2: wt_abs_core.h */
 constexpr int ABS_COUNT_THREADS = 256;
@@ -481,15 +481,10 @@ struct AbsTable {
     Taps tp;
 };
 static_assert(sizeof(AbsTable) + 8 <= 4096, "k_abs_tiny's kernel argument");
-void launch_abs_init(wtp_abs_result* res, int n, float* thr_word, uint32_t thr_bits, hipStream_t s);
-void launch_abs_zero(float* p, int64_t n, hipStream_t s);
-void launch_abs_tiny(const AbsTable& t, wtp_abs_result* res, hipStream_t s);
-void launch_abs_count(const float* x, int64_t n, unsigned long long* dst, wtp_abs_result* rec,
-                      const wtp_abs_result& init, hipStream_t s);
 /* ---- the absolute-threshold sweep (abs.hip, wtp_prune_abs_sweep_f32) ----
- * k_abs_tiny_sweep: k_abs_tiny's wave, lane and arena scheme; a wave reads its images once, runs
- * the forward once and then every threshold's inverse over the raw coefficients it kept in LDS
- * (wt_abs_sweep_core.h).  A segment carries an output per threshold, so a launch takes fewer
+ * k_abs_tiny_sweep: k_abs_tiny's wave, lane and arena scheme (on wt_tiny_arena.h's device part); a
+ * wave reads its images once, runs the forward once and then every threshold's inverse over the
+ * raw coefficients it kept in LDS (wt_abs_sweep_core.h).  A segment carries an output per threshold, so a launch takes fewer
  * tensors than ABS_MAX_SEG.  Records are threshold-major: tensor t at threshold k is record
  * k * ntensors + t. */
 constexpr int ABS_SWEEP_MAX_THR = 8;   /* = WTP_ABS_SWEEP_MAX_THR */
@@ -517,13 +512,18 @@ struct AbsSweepTable {
     Taps tp;
 };
 static_assert(sizeof(AbsSweepTable) + 8 <= 4096, "k_abs_tiny_sweep's kernel argument");
-/* the call's first launch: every record zero, threshold word k at thr_words[k] */
-void launch_abs_sweep_init(wtp_abs_result* res, int n, float* thr_words, const AbsThr& thr, hipStream_t s);
-void launch_abs_tiny_sweep(const AbsSweepTable& t, wtp_abs_result* res, hipStream_t s);
+/* The launchers of both entries; to all but the tiny kernels the ordinary call is a sweep of one
+ * threshold.  The call's first launch: n records zero, threshold word k at thr_words[k] (null:
+ * no kernel of the call reads them from memory) */
+void launch_abs_init(wtp_abs_result* res, int n, float* thr_words, const AbsThr& thr, hipStream_t s);
+void launch_abs_tiny(const AbsTable& t, wtp_abs_result* res, hipStream_t s);      /* k_abs_tiny */
+void launch_abs_tiny(const AbsSweepTable& t, wtp_abs_result* res, hipStream_t s); /* k_abs_tiny_sweep */
 /* count_nonzero(x) once, added to nonzero_in of the tensor's thr.n records (rec, rec + stride,
  * ...), each of which also gets its fixed fields (init's, with its own threshold) */
-void launch_abs_count_sweep(const float* x, int64_t n, wtp_abs_result* rec, int64_t stride, const AbsThr& thr,
-                            const wtp_abs_result& init, hipStream_t s);
+void launch_abs_count_in(const float* x, int64_t n, wtp_abs_result* rec, int64_t stride, const AbsThr& thr,
+                         const wtp_abs_result& init, hipStream_t s);
+void launch_abs_zero(float* p, int64_t n, hipStream_t s);
+void launch_abs_count(const float* x, int64_t n, unsigned long long* dst, hipStream_t s); /* count_nonzero(x) added to *dst */
 /* ---- the extension modes (modes.hip; arithmetic and geometry: wt_modes_core.h) ----
  * one level of one tensor, per-point: the two analysis passes through tL / tH, the two synthesis
  * passes through tL / tH (the level's output cropped to oH x oW) */

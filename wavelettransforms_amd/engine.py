@@ -98,6 +98,51 @@ def _as_desc(tensors, outs):
     return arr
 
 
+def _prepare(tensors, outs, nsets=None, sets_of=None, no_outs=False):
+    """What every launcher starts with: the checked tensors made contiguous, the default or checked
+    outputs (one list; under nsets a list of nsets lists, one per `sets_of`; none under no_outs),
+    the tensor count, their device and the descriptor array -- the last two None for an empty
+    list, which the caller answers before it touches a device.  A sweep's descriptors carry the
+    inputs alone: its outputs go to the library as _out_ptrs."""
+    check_tensors(tensors)
+    tensors = [x.contiguous() for x in tensors]
+    if no_outs:
+        outs = None
+    elif nsets is None:
+        if outs is None:
+            outs = [torch.empty_like(x) for x in tensors]
+        else:
+            check_outs(tensors, outs)
+    elif outs is None:
+        outs = [[torch.empty_like(x) for x in tensors] for _ in range(nsets)]
+    else:
+        if len(outs) != nsets:
+            raise ValueError("wavelettransforms_amd: %d output sets for %d %s" % (len(outs), nsets, sets_of))
+        for o in outs:
+            check_outs(tensors, o)
+    n = len(tensors)
+    if n == 0:
+        return tensors, outs, 0, None, None
+    return tensors, outs, n, tensors[0].device, _as_desc(tensors, tensors if nsets is not None else outs)
+
+
+def _current(device, stream):
+    return torch.cuda.current_stream(device) if stream is None else stream
+
+
+def _out_ptrs(outs, n):
+    """A sweep's output pointers, set-major: set k of tensor t at [k * n + t]."""
+    return (ctypes.c_void_p * max(1, len(outs) * n))(*[y.data_ptr() if y.numel() else None for o in outs for y in o])
+
+
+def _decode_blocks(res, nsets, n, nbytes, decode_fn):
+    """A sweep's records, one decoded block of n per set."""
+    if res is None:
+        return [[] for _ in range(nsets)]
+    blocks = res.view(nsets, n * nbytes)
+    return [decode_fn(blocks[k], n) for k in range(nsets)]
+
+
 def raise_for(code, tensors, wavelet):
     """Map a library status to the exception the reference path raises at that point."""
     L = N.lib()
@@ -174,27 +219,18 @@ def launch(tensors, wavelet, level, pct, outs=None, carry_level=True, stream=Non
     mid = mode_id(mode)
     if mid and flatten:
         raise ValueError("wavelettransforms_amd: flatten=True runs under mode='periodization' only")
-    check_tensors(tensors)
-    tensors = [x.contiguous() for x in tensors]
-    if outs is None:
-        outs = [torch.empty_like(x) for x in tensors]
-    else:
-        check_outs(tensors, outs)
-    n = len(tensors)
+    tensors, outs, n, device, desc = _prepare(tensors, outs)
     if n == 0:
         return outs, None
-    device = tensors[0].device
     L = N.lib()
     wid = wavelet_id(wavelet)
-    desc = _as_desc(tensors, outs)
     flags = ((WTP_CARRY_LEVEL if carry_level else 0) | (WTP_FLATTEN if flatten else 0)
              | (WTP_NO_RESIDENT if no_resident else 0))
     if mid:
         nbytes = L.wtp_workspace_size_mode(desc, n, wid, int(level), flags, mid)
     else:
         nbytes = L.wtp_workspace_size_ex(desc, n, wid, int(level), flags)
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
+    stream = _current(device, stream)
     ws = workspace(device, nbytes if nbytes else 256, stream)
     if results is None:
         res = _results(n, device, stream)
@@ -357,21 +393,12 @@ def launch_abs(tensors, wavelet, level, threshold, outs=None, stream=None):
     to zero, the inverse, the crop; ndim < 2 tensors are masked as they are.  Returns (outs,
     results_dev) without synchronising; results_dev is a uint8 CUDA tensor of len(tensors)
     wtp_abs_result records (decode_abs).  outs may be the inputs (in place)."""
-    check_tensors(tensors)
-    tensors = [x.contiguous() for x in tensors]
-    if outs is None:
-        outs = [torch.empty_like(x) for x in tensors]
-    else:
-        check_outs(tensors, outs)
-    n = len(tensors)
+    tensors, outs, n, device, desc = _prepare(tensors, outs)
     if n == 0:
         return outs, None
-    device = tensors[0].device
     L = N.lib()
     wid = wavelet_id(wavelet)
-    desc = _as_desc(tensors, outs)
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
+    stream = _current(device, stream)
     nbytes = L.wtp_abs_workspace_size(desc, n, wid, int(level))
     # scratch of this entry alone: never the selection entries' workspace (include/wtprune.h)
     ws = workspace(device, nbytes if nbytes else 256, stream, kind="abs")
@@ -419,32 +446,19 @@ def launch_abs_sweep(tensors, wavelet, level, thresholds, outs=None, stream=None
     one output of a tensor may be the tensor itself."""
     thresholds = [float(v) for v in thresholds]
     nthr = len(thresholds)
-    check_tensors(tensors)
-    tensors = [x.contiguous() for x in tensors]
-    if outs is None:
-        outs = [[torch.empty_like(x) for x in tensors] for _ in range(nthr)]
-    else:
-        if len(outs) != nthr:
-            raise ValueError("wavelettransforms_amd: %d output sets for %d thresholds" % (len(outs), nthr))
-        for o in outs:
-            check_outs(tensors, o)
-    n = len(tensors)
+    tensors, outs, n, device, desc = _prepare(tensors, outs, nthr, "thresholds")
     if n == 0:
         return outs, None
-    device = tensors[0].device
     L = N.lib()
     wid = wavelet_id(wavelet)
-    desc = _as_desc(tensors, tensors)
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
+    stream = _current(device, stream)
     nbytes = L.wtp_abs_sweep_workspace_size(desc, n, wid, int(level), nthr)
     # scratch of the absolute-threshold entries alone: never the selection entries' workspace
     ws = workspace(device, nbytes if nbytes else 256, stream, kind="abs")
     with torch.cuda.stream(stream):
         res = torch.empty(max(1, nthr) * n * N.ABS_RESULT_BYTES, dtype=torch.uint8, device=device)
     tarr = (ctypes.c_double * max(1, nthr))(*thresholds)
-    optr = (ctypes.c_void_p * max(1, nthr * n))(*[y.data_ptr() if y.numel() else None for o in outs for y in o])
-    rc = L.wtp_prune_abs_sweep_f32(desc, n, wid, int(level), tarr, nthr, optr, ws.data_ptr(), ws.numel(),
+    rc = L.wtp_prune_abs_sweep_f32(desc, n, wid, int(level), tarr, nthr, _out_ptrs(outs, n), ws.data_ptr(), ws.numel(),
                                    res.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
     if rc != N.WTP_OK:
         raise_for(rc, tensors, wavelet)
@@ -456,11 +470,7 @@ def prune_abs_sweep(tensors, wavelet, level, thresholds, outs=None):
     tensor t at thresholds[k] (decode_abs() of block k)."""
     thresholds = list(thresholds)
     outs, res = launch_abs_sweep(tensors, wavelet, level, thresholds, outs=outs)
-    nthr, n = len(thresholds), len(tensors)
-    if res is None:
-        return outs, [[] for _ in range(nthr)]
-    blocks = res.view(nthr, n * N.ABS_RESULT_BYTES)
-    return outs, [decode_abs(blocks[k], n) for k in range(nthr)]
+    return outs, _decode_blocks(res, len(thresholds), len(tensors), N.ABS_RESULT_BYTES, decode_abs)
 
 
 WTP_SWEEP_MAX_PCT, WTP_SWEEP_THRESHOLDS_ONLY, MODE_SWEEP = 8, 16, 5  # include/wtprune.h
@@ -478,35 +488,19 @@ def launch_sweep(tensors, wavelet, level, pcts, outs=None, carry_level=True, thr
     carry the thresholds with zero_count 0."""
     pcts = [float(p) for p in pcts]
     npct = len(pcts)
-    check_tensors(tensors)
-    tensors = [x.contiguous() for x in tensors]
-    if thresholds_only:
-        outs = None
-    elif outs is None:
-        outs = [[torch.empty_like(x) for x in tensors] for _ in range(npct)]
-    else:
-        if len(outs) != npct:
-            raise ValueError("wavelettransforms_amd: %d output sets for %d percentiles" % (len(outs), npct))
-        for o in outs:
-            check_outs(tensors, o)
-    n = len(tensors)
+    tensors, outs, n, device, desc = _prepare(tensors, outs, npct, "percentiles", no_outs=thresholds_only)
     if n == 0:
         return outs, None
-    device = tensors[0].device
     L = N.lib()
     wid = wavelet_id(wavelet)
-    desc = _as_desc(tensors, tensors)
     flags = (WTP_CARRY_LEVEL if carry_level else 0) | (WTP_SWEEP_THRESHOLDS_ONLY if thresholds_only else 0)
-    if stream is None:
-        stream = torch.cuda.current_stream(device)
+    stream = _current(device, stream)
     nbytes = L.wtp_sweep_workspace_size(desc, n, wid, int(level), npct, flags)
     # scratch of this entry alone: never the selection entries' workspace (include/wtprune.h)
     ws = workspace(device, nbytes if nbytes else 256, stream, kind="sweep")
     res = _results(max(1, npct) * n, device, stream)
     parr = (ctypes.c_double * max(1, npct))(*pcts)
-    optr = None
-    if outs is not None:
-        optr = (ctypes.c_void_p * (npct * n))(*[y.data_ptr() if y.numel() else None for o in outs for y in o])
+    optr = None if outs is None else _out_ptrs(outs, n)
     rc = L.wtp_prune_sweep_f32(desc, n, wid, int(level), parr, npct, flags, optr, ws.data_ptr(), ws.numel(),
                                res.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
     if rc != N.WTP_OK:
@@ -520,34 +514,22 @@ def prune_sweep(tensors, wavelet, level, pcts, outs=None, carry_level=True, thre
     pcts = list(pcts)
     outs, res = launch_sweep(tensors, wavelet, level, pcts, outs=outs, carry_level=carry_level,
                              thresholds_only=thresholds_only)
-    npct, n = len(pcts), len(tensors)
-    if res is None:
-        return outs, [[] for _ in range(npct)]
-    blocks = res.view(npct, n * N.RESULT_BYTES)
-    return outs, [decode(blocks[k], n) for k in range(npct)]
+    return outs, _decode_blocks(res, len(pcts), len(tensors), N.RESULT_BYTES, decode)
 
 
 def min_prune(tensors, fraction, outs=None):
     """percentage_min_pruning (min_weight_pruning.py:66-74) of every tensor (CUDA float32) in one
     launch sequence: zero the int(numel * fraction) smallest |w|; ties at the boundary lowest
     flat index first.  Returns (outs, records); outs may be the inputs (in place)."""
-    check_tensors(tensors)
-    tensors = [x.contiguous() for x in tensors]
-    if outs is None:
-        outs = [torch.empty_like(x) for x in tensors]
-    else:
-        check_outs(tensors, outs)
-    n = len(tensors)
+    tensors, outs, n, device, desc = _prepare(tensors, outs)
     if n == 0:
         return outs, []
-    device = tensors[0].device
     L = N.lib()
-    desc = _as_desc(tensors, outs)
     nbytes = L.wtp_min_prune_workspace_size(desc, n, float(fraction))
     ws = workspace(device, nbytes if nbytes else 256)
     res = torch.empty(n * N.RESULT_BYTES, dtype=torch.uint8, device=device)
     rc = L.wtp_min_prune_f32(desc, n, float(fraction), ws.data_ptr(), ws.numel(), res.data_ptr(),
-                             ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+                             ctypes.c_void_p(_current(device, None).cuda_stream))
     if rc != N.WTP_OK:
         msg = N.last_error()
         if rc == N.WTP_EARG and "NaN" in msg:
@@ -562,23 +544,15 @@ def random_prune(tensors, prune_counts, seed, outs=None):
     """random_pruning's per-layer step (random_pruning.py:53-56) for every tensor (CUDA float32)
     in one launch sequence: zero randperm(numel)[:k] -- k distinct flat positions of a keyed
     permutation (csrc/wt_perm.h; tensor index t keys tensor t).  Returns (outs, records)."""
-    check_tensors(tensors)
-    tensors = [x.contiguous() for x in tensors]
-    if outs is None:
-        outs = [torch.empty_like(x) for x in tensors]
-    else:
-        check_outs(tensors, outs)
-    n = len(tensors)
+    tensors, outs, n, device, desc = _prepare(tensors, outs)
     if n == 0:
         return outs, []
     if len(prune_counts) != n:
         raise ValueError("random_prune: %d prune counts for %d tensors" % (len(prune_counts), n))
-    device = tensors[0].device
-    desc = _as_desc(tensors, outs)
     ks = (ctypes.c_int64 * n)(*[int(k) for k in prune_counts])
     res = torch.empty(n * N.RESULT_BYTES, dtype=torch.uint8, device=device)
     rc = N.lib().wtp_random_prune_f32(desc, n, ks, ctypes.c_uint64(int(seed) & (2**64 - 1)), res.data_ptr(),
-                                      ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+                                      ctypes.c_void_p(_current(device, None).cuda_stream))
     if rc != N.WTP_OK:
         raise_for(rc, tensors, None)
     return outs, decode(res, n)
@@ -617,91 +591,84 @@ def threshold(x, pct, out=None):
     return out, decode(res, 1)[0]
 
 
-def wavedec2_packed(x, wavelet, level):
-    """pywt.coeffs_to_array(pywt.wavedec2(x, wavelet, level, 'periodization', axes=(-2,-1)))[0] on the GPU."""
+def _wavedec2(x, wavelet, level, mid=None):
+    """mid=None: the periodized C entries (which report an unknown wavelet differently); else WTP_MODE_*"""
     check_tensors([x])
     x = x.contiguous()
     L = N.lib()
+    wid, level = wavelet_id(wavelet), int(level)
     H, W = x.shape[-2], x.shape[-1]
     B = x.numel() // max(1, H * W)
     pr, pc = ctypes.c_int64(), ctypes.c_int64()
-    if L.wtp_packed_shape(H, W, int(level), ctypes.byref(pr), ctypes.byref(pc)) != 0:
+    if mid is None:
+        rc = L.wtp_packed_shape(H, W, level, ctypes.byref(pr), ctypes.byref(pc))
+    else:
+        rc = L.wtp_packed_shape_mode(H, W, wid, level, mid, ctypes.byref(pr), ctypes.byref(pc))
+    if rc != 0:
         raise ValueError(N.last_error())
     P = torch.empty(tuple(x.shape[:-2]) + (pr.value, pc.value), dtype=torch.float32, device=x.device)
-    nb = L.wtp_dwt_workspace_size(B, H, W, int(level))
-    ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=x.device)
-    rc = L.wtp_wavedec2_f32(x.data_ptr(), P.data_ptr(), B, H, W, wavelet_id(wavelet), int(level), ws.data_ptr(),
-                            ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+    ws = _component_ws(B, H, W, wid, level, mid, x.device)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    if mid is None:
+        rc = L.wtp_wavedec2_f32(x.data_ptr(), P.data_ptr(), B, H, W, wid, level, ws.data_ptr(), ws.numel(), stream)
+    else:
+        rc = L.wtp_wavedec2_mode_f32(x.data_ptr(), P.data_ptr(), B, H, W, wid, level, mid, ws.data_ptr(), ws.numel(), stream)
     if rc != 0:
         raise_for(rc, [x], wavelet)
     return P
 
 
-def waverec2_packed(P, shape, wavelet, level, thr32=None):
-    """array_to_coeffs + waverec2 + crop to `shape` (optionally thresholding on load)."""
+def _waverec2(P, shape, wavelet, level, mid=None, thr32=None):
     L = N.lib()
+    wid, level = wavelet_id(wavelet), int(level)
     H, W = shape[-2], shape[-1]
     B = 1
     for s in shape[:-2]:
         B *= s
     out = torch.empty(tuple(shape), dtype=torch.float32, device=P.device)
-    nb = L.wtp_dwt_workspace_size(B, H, W, int(level))
-    ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=P.device)
+    ws = _component_ws(B, H, W, wid, level, mid, P.device)
     thr = None
     if thr32 is not None:
         thr = torch.tensor([thr32], dtype=torch.float32, device=P.device)
-    rc = L.wtp_waverec2_f32(P.contiguous().data_ptr(), out.data_ptr(), B, H, W, wavelet_id(wavelet), int(level),
-                            thr.data_ptr() if thr is not None else None, ws.data_ptr(), ws.numel(),
-                            ctypes.c_void_p(torch.cuda.current_stream(P.device).cuda_stream))
+    thr_ptr = thr.data_ptr() if thr is not None else None
+    stream = ctypes.c_void_p(torch.cuda.current_stream(P.device).cuda_stream)
+    if mid is None:
+        rc = L.wtp_waverec2_f32(P.contiguous().data_ptr(), out.data_ptr(), B, H, W, wid, level, thr_ptr, ws.data_ptr(),
+                                ws.numel(), stream)
+    else:
+        rc = L.wtp_waverec2_mode_f32(P.contiguous().data_ptr(), out.data_ptr(), B, H, W, wid, level, mid, thr_ptr,
+                                     ws.data_ptr(), ws.numel(), stream)
     if rc != 0:
         raise_for(rc, [P], wavelet)
     return out
+
+
+def _component_ws(B, H, W, wid, level, mid, device):
+    """the level temps of a component call"""
+    L = N.lib()
+    nb = L.wtp_dwt_workspace_size(B, H, W, level) if mid is None else L.wtp_dwt_workspace_size_mode(B, H, W, wid, level, mid)
+    return torch.empty(max(nb, 256), dtype=torch.uint8, device=device)
+
+
+def wavedec2_packed(x, wavelet, level):
+    """pywt.coeffs_to_array(pywt.wavedec2(x, wavelet, level, 'periodization', axes=(-2,-1)))[0] on the GPU."""
+    return _wavedec2(x, wavelet, level)
+
+
+def waverec2_packed(P, shape, wavelet, level, thr32=None):
+    """array_to_coeffs + waverec2 + crop to `shape` (optionally thresholding on load)."""
+    return _waverec2(P, shape, wavelet, level, None, thr32)
 
 
 def wavedec2_packed_mode(x, wavelet, level, mode):
     """pywt.coeffs_to_array(pywt.wavedec2(x, wavelet, mode, level, axes=(-2,-1)))[0] on the GPU
     (wtp_wavedec2_mode_f32: the level as given, padding cells zero)."""
-    mid = mode_id(mode)
-    check_tensors([x])
-    x = x.contiguous()
-    L = N.lib()
-    wid = wavelet_id(wavelet)
-    H, W = x.shape[-2], x.shape[-1]
-    B = x.numel() // max(1, H * W)
-    pr, pc = ctypes.c_int64(), ctypes.c_int64()
-    if L.wtp_packed_shape_mode(H, W, wid, int(level), mid, ctypes.byref(pr), ctypes.byref(pc)) != 0:
-        raise ValueError(N.last_error())
-    P = torch.empty(tuple(x.shape[:-2]) + (pr.value, pc.value), dtype=torch.float32, device=x.device)
-    nb = L.wtp_dwt_workspace_size_mode(B, H, W, wid, int(level), mid)
-    ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=x.device)
-    rc = L.wtp_wavedec2_mode_f32(x.data_ptr(), P.data_ptr(), B, H, W, wid, int(level), mid, ws.data_ptr(), ws.numel(),
-                                 ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-    if rc != 0:
-        raise_for(rc, [x], wavelet)
-    return P
+    return _wavedec2(x, wavelet, level, mode_id(mode))
 
 
 def waverec2_packed_mode(P, shape, wavelet, level, mode, thr32=None):
     """array_to_coeffs + waverec2(mode) + crop to `shape` (optionally thresholding on load)."""
-    mid = mode_id(mode)
-    L = N.lib()
-    wid = wavelet_id(wavelet)
-    H, W = shape[-2], shape[-1]
-    B = 1
-    for s in shape[:-2]:
-        B *= s
-    out = torch.empty(tuple(shape), dtype=torch.float32, device=P.device)
-    nb = L.wtp_dwt_workspace_size_mode(B, H, W, wid, int(level), mid)
-    ws = torch.empty(max(nb, 256), dtype=torch.uint8, device=P.device)
-    thr = None
-    if thr32 is not None:
-        thr = torch.tensor([thr32], dtype=torch.float32, device=P.device)
-    rc = L.wtp_waverec2_mode_f32(P.contiguous().data_ptr(), out.data_ptr(), B, H, W, wid, int(level), mid,
-                                 thr.data_ptr() if thr is not None else None, ws.data_ptr(), ws.numel(),
-                                 ctypes.c_void_p(torch.cuda.current_stream(P.device).cuda_stream))
-    if rc != 0:
-        raise_for(rc, [P], wavelet)
-    return out
+    return _waverec2(P, shape, wavelet, level, mode_id(mode), thr32)
 
 
 def synth(shape, seed, tensor_id, e, device="cuda"):
