@@ -22,6 +22,7 @@
  *                                   main_pruning.py:186 over its thresholds, in one call
  *   wtp_prune_abs_sweep_f32         multi_resolution_analysis of dwt_pruning_NoEntropy.py:29-60 at a
  *                                   grid of absolute thresholds (the same loop), in one call
+ *   wtp_prune_f16                   multi_resolution_analysis on float16 weights (model.half())
  *   wtp_synth_f32                   (test/bench input generator, no reference counterpart)
  */
 #ifndef WTPRUNE_H
@@ -71,6 +72,7 @@ typedef struct wtp_result {
                                4 the one-launch small path (exact three-digit radix select);
                                + 8 (9, 10, 11): the fused selection's patch window missed the ranks
                                and the segment was selected again over its coefficients;
+                               5 a sweep's record; 6 a float16 tensor that got no transform (wtp_prune_f16);
                                99 = the resident launch's grid was not co-resident (results invalid) */
 } wtp_result;
 
@@ -285,6 +287,40 @@ int wtp_prune_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id,
                         const double* pcts /* host */, int npct, int flags,
                         float* const* outs /* host array of npct * ntensors device pointers */, void* workspace,
                         size_t workspace_bytes, wtp_result* results_dev /* npct * ntensors */, wtp_stream_t stream);
+
+/* ---- float16 weights: multi_resolution_analysis on the tensors of model.half() ----
+ * The reference takes float16 weights as they come (dwt_pruning.py:56 .numpy(), :61 / :84 rebuild
+ * with dtype=weight.dtype); wtp_prune_f16 is wtp_prune_mode_f32 for them.  The descriptor is the
+ * same wtp_tensor, but its `in` / `out` are read and written as IEEE binary16 words (numel of
+ * them, 2-byte aligned; cast the pointers).  Per tensor, what NumPy 1.x and PyWavelets 1.1.1 do:
+ *   a tensor that gets a transform (ndim >= 2 and a clamped level >= 1, in any mode): wavedec2
+ *     widens to float32, so it runs exactly as wtp_prune_mode_f32 on float32(w) and the float32
+ *     result is narrowed once, round to nearest even; its record is that call's, with zero_count
+ *     counted AFTER the narrowing (a float32 result of at most 2^-25 in magnitude is a zero);
+ *   a tensor that gets none (ndim < 2, or level 0 after the clamp): everything stays float16.
+ *     thr64 is np.percentile of the float16 array -- the two order statistics' difference is
+ *     NumPy's half subtraction (the float32 difference rounded to half), the blend runs in
+ *     float64 -- and the compare |w| < thr runs in float16 on half(thr64) (one rounding from
+ *     float64): thr32_bits holds that value widened to float32, max_abs_bits the widened float16
+ *     maximum, coeff_numel = numel, path = WTP_PATH_HALF.  Pruned words are +0, the others keep
+ *     their bits.  The selection is exact by construction: |w| has 2^15 possible keys, found by
+ *     two histogram passes (11 + 4 bits); no sample, no window, no other path.
+ * Not covered: inputs with |w| >= 65000, +-inf or NaN (NumPy changes the compare's type there, or
+ * the threshold is NaN).  They are safe to pass, but no parity with the reference is claimed.
+ * flags: WTP_CARRY_LEVEL as elsewhere; WTP_NO_RESIDENT is accepted and ignored (no float16 tensor
+ * reaches the resident launch); WTP_FLATTEN is WTP_EARG (the flattened mode is float32 only).
+ * Everything else as wtp_prune_mode_f32: validation of every tensor in the reference's order before
+ * any device work (a tensor of more than 2^31-1 weights is WTP_EARG: the histogram counts are 32
+ * bits wide), no allocation, no synchronisation, capturable, out may alias in.
+ * Workspace: wtp_workspace_size_f16 bytes (0 if the request is invalid), zeroed once with
+ * wtp_workspace_init and this entry's own: it begins with the float32 call's workspace for the
+ * transformed tensors, kept as that call keeps it, followed by scratch that every call zeroes
+ * itself (do not hand it to a float32 entry). */
+#define WTP_PATH_HALF 6
+size_t wtp_workspace_size_f16(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int flags,
+                              int mode_id);
+int wtp_prune_f16(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, double pct, int flags,
+                  int mode_id, void* workspace, size_t workspace_bytes, wtp_result* results_dev, wtp_stream_t stream);
 
 /* percentile_based_thresholding(arr, pct) on n device floats: out = where(|in| < thr, 0, in) */
 int wtp_threshold_f32(const float* in, float* out, int64_t n, double pct, void* workspace,

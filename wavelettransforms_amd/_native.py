@@ -81,6 +81,8 @@ def lib():
             "wtp_packed_shape_mode": ([i64, i64, i32, i32, i32, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
             "wtp_workspace_size_mode": ([tp, i32, i32, i32, i32, i32], sz),
             "wtp_prune_mode_f32": ([tp, i32, i32, i32, f64, i32, i32, vp, sz, vp, vp], i32),
+            "wtp_workspace_size_f16": ([tp, i32, i32, i32, i32, i32], sz),
+            "wtp_prune_f16": ([tp, i32, i32, i32, f64, i32, i32, vp, sz, vp, vp], i32),
             "wtp_dwt_workspace_size_mode": ([i64, i64, i64, i32, i32, i32], sz),
             "wtp_wavedec2_mode_f32": ([vp, vp, i64, i64, i64, i32, i32, i32, vp, sz, vp], i32),
             "wtp_waverec2_mode_f32": ([vp, vp, i64, i64, i64, i32, i32, i32, vp, vp, sz, vp], i32),

@@ -16,6 +16,12 @@ identical); weights that live on the CPU are moved to the current CUDA device fo
 computation and the results are returned on the weight's own device; of PyWavelets' modes
 periodization, zero, constant, symmetric, reflect and periodic exist (smooth, antisymmetric and
 antireflect raise NotImplementedError).
+
+float16 weights (model.half()) go through multi_resolution_analysis, prune_layer_weights and
+wavelet_pruning as they do through the reference, and come back as float16: a tensor that gets a
+transform is computed in float32 and narrowed once, one that gets none stays in float16 with
+NumPy's float16 percentile and compare (wtp_prune_f16).  All tensors of a call share one dtype.
+multi_resolution_analysis_sweep, flatten=True and percentile_based_thresholding take float32 only.
 """
 import os
 from typing import List, Tuple
@@ -63,8 +69,10 @@ def _cuda(x):
 
 
 def _print_threshold_line(percentile, rec):
-    # reference :29-30 prints np.float64 threshold and np.float32 max (shortest repr each)
-    print(f"Percentile: {percentile}, Threshold: {np.float64(rec['thr64'])}, Max Coeff: {rec['max_abs']}")
+    # reference :29-30 prints the np.float64 threshold and np.max of the array it thresholded: an
+    # np.float32, or an np.float16 for a float16 tensor that got no transform (engine.MODE_HALF)
+    mx = np.float16(rec["max_abs"]) if rec.get("path") == engine.MODE_HALF else rec["max_abs"]
+    print(f"Percentile: {percentile}, Threshold: {np.float64(rec['thr64'])}, Max Coeff: {mx}")
 
 
 def percentile_based_thresholding(coeff_arr, percentile=90):

@@ -71,14 +71,16 @@ def _results(n, device, stream):
         return torch.empty(n * N.RESULT_BYTES, dtype=torch.uint8, device=device)
 
 
-def check_outs(tensors, outs):
-    """Caller-supplied outputs must be dense float32 CUDA tensors shaped like their inputs: the
-    library writes numel contiguous floats from out.data_ptr()."""
+def check_outs(tensors, outs, dtype=torch.float32):
+    """Caller-supplied outputs must be dense CUDA tensors of the inputs' dtype (float32; float16
+    where the entry takes it) shaped like their inputs: the library writes numel contiguous words
+    from out.data_ptr()."""
     if len(outs) != len(tensors):
         raise ValueError("wavelettransforms_amd: %d outputs for %d tensors" % (len(outs), len(tensors)))
     for i, (x, y) in enumerate(zip(tensors, outs)):
-        if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dtype != torch.float32:
-            raise TypeError("wavelettransforms_amd: outs[%d] must be a float32 CUDA tensor" % i)
+        if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dtype != dtype:
+            raise TypeError("wavelettransforms_amd: outs[%d] must be a %s CUDA tensor"
+                            % (i, str(dtype).replace("torch.", "")))
         if y.device != x.device or y.numel() != x.numel():
             raise ValueError("wavelettransforms_amd: outs[%d] has %d elements on %s, input %d on %s"
                              % (i, y.numel(), y.device, x.numel(), x.device))
@@ -98,13 +100,14 @@ def _as_desc(tensors, outs):
     return arr
 
 
-def _prepare(tensors, outs, nsets=None, sets_of=None, no_outs=False):
+def _prepare(tensors, outs, nsets=None, sets_of=None, no_outs=False, allow_half=False):
     """What every launcher starts with: the checked tensors made contiguous, the default or checked
     outputs (one list; under nsets a list of nsets lists, one per `sets_of`; none under no_outs),
     the tensor count, their device and the descriptor array -- the last two None for an empty
     list, which the caller answers before it touches a device.  A sweep's descriptors carry the
-    inputs alone: its outputs go to the library as _out_ptrs."""
-    check_tensors(tensors)
+    inputs alone: its outputs go to the library as _out_ptrs.  allow_half: the entry takes a list
+    of float16 tensors too (launch(); its outputs are then float16)."""
+    dtype = check_tensors(tensors, allow_half=allow_half)
     tensors = [x.contiguous() for x in tensors]
     if no_outs:
         outs = None
@@ -112,7 +115,7 @@ def _prepare(tensors, outs, nsets=None, sets_of=None, no_outs=False):
         if outs is None:
             outs = [torch.empty_like(x) for x in tensors]
         else:
-            check_outs(tensors, outs)
+            check_outs(tensors, outs, dtype)
     elif outs is None:
         outs = [[torch.empty_like(x) for x in tensors] for _ in range(nsets)]
     else:
@@ -176,14 +179,34 @@ def _recon_numel(x):
     return n
 
 
-def check_tensors(tensors):
+def check_tensors(tensors, allow_half=False):
+    """Every tensor a float32 CUDA tensor; under allow_half (the percentile path of launch() /
+    prune()) a list whose tensors are ALL float16 passes too.  Returns the list's dtype."""
+    dtype = list_dtype(tensors, allow_half)
     for x in tensors:
         if not isinstance(x, torch.Tensor):
             raise TypeError("expected torch.Tensor, got %r" % type(x))
         if not x.is_cuda:
             raise ValueError("wavelettransforms_amd runs on the GPU: tensor on %s (move it to cuda)" % x.device)
-        if x.dtype != torch.float32:
-            raise TypeError("wavelettransforms_amd: float32 weights only (got %s)" % x.dtype)
+        check_dtype(x, dtype)
+    return dtype
+
+
+def list_dtype(tensors, allow_half=False):
+    """The dtype a list is held to: float32, or float16 when the entry takes it and some tensor is one."""
+    if allow_half and any(isinstance(x, torch.Tensor) and x.dtype == torch.float16 for x in tensors):
+        return torch.float16
+    return torch.float32
+
+
+def check_dtype(x, dtype):
+    """TypeError unless x has the list's dtype (bfloat16 and float64 never pass: the reference's
+    .numpy() refuses the first, and the path is not built for the second)."""
+    if x.dtype != dtype:
+        if dtype == torch.float16:
+            raise TypeError("wavelettransforms_amd: float16 and %s weights in one call (all float16 or all "
+                            "float32)" % x.dtype)
+        raise TypeError("wavelettransforms_amd: float32 weights only (got %s)" % x.dtype)
 
 
 WTP_CARRY_LEVEL, WTP_FLATTEN, WTP_NO_RESIDENT = 1, 2, 4  # include/wtprune.h
@@ -215,23 +238,32 @@ def launch(tensors, wavelet, level, pct, outs=None, carry_level=True, stream=Non
     A record whose path reads MODE_FAULT was not computed (the resident launch's grid was not
     co-resident; nothing was stored for that tensor): prune() re-runs such tensors itself.
     mode: the PyWavelets signal-extension mode of the transform (wtp_prune_mode_f32).
+    A list of float16 tensors (all of them: model.half()) runs wtp_prune_f16 and gives float16
+    outputs, as the reference does with such weights; outs must then be float16 and flatten=True
+    is a TypeError (the flattened mode is float32 only).
     results: optional uint8 CUDA tensor of len(tensors) records (8-byte aligned) to write into."""
     mid = mode_id(mode)
     if mid and flatten:
         raise ValueError("wavelettransforms_amd: flatten=True runs under mode='periodization' only")
-    tensors, outs, n, device, desc = _prepare(tensors, outs)
+    tensors, outs, n, device, desc = _prepare(tensors, outs, allow_half=True)
+    half = n > 0 and tensors[0].dtype == torch.float16
+    if half and flatten:
+        raise TypeError("wavelettransforms_amd: flatten=True takes float32 weights only (got torch.float16)")
     if n == 0:
         return outs, None
     L = N.lib()
     wid = wavelet_id(wavelet)
     flags = ((WTP_CARRY_LEVEL if carry_level else 0) | (WTP_FLATTEN if flatten else 0)
              | (WTP_NO_RESIDENT if no_resident else 0))
-    if mid:
+    if half:
+        nbytes = L.wtp_workspace_size_f16(desc, n, wid, int(level), flags, mid)
+    elif mid:
         nbytes = L.wtp_workspace_size_mode(desc, n, wid, int(level), flags, mid)
     else:
         nbytes = L.wtp_workspace_size_ex(desc, n, wid, int(level), flags)
     stream = _current(device, stream)
-    ws = workspace(device, nbytes if nbytes else 256, stream)
+    # the float16 entry's workspace is its own (include/wtprune.h)
+    ws = workspace(device, nbytes if nbytes else 256, stream, kind="f16" if half else None)
     if results is None:
         res = _results(n, device, stream)
     else:
@@ -239,7 +271,10 @@ def launch(tensors, wavelet, level, pct, outs=None, carry_level=True, stream=Non
                 or results.data_ptr() % 8):
             raise ValueError("wavelettransforms_amd: results must be %d 8-byte aligned CUDA bytes" % (n * N.RESULT_BYTES))
         res = results
-    if mid:
+    if half:
+        rc = L.wtp_prune_f16(desc, n, wid, int(level), float(pct), flags, mid, ws.data_ptr(), ws.numel(),
+                             res.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    elif mid:
         rc = L.wtp_prune_mode_f32(desc, n, wid, int(level), float(pct), flags, mid, ws.data_ptr(), ws.numel(),
                                   res.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
     else:
@@ -252,6 +287,7 @@ def launch(tensors, wavelet, level, pct, outs=None, carry_level=True, stream=Non
 
 MODE_FAULT = 99  # WTP_PATH_FAULT: the resident launch timed out for this tensor and stored nothing
 MODE_SMALL = 4   # WTP_PATH_SMALL: the whole call ran as one launch (csrc/small.hip)
+MODE_HALF = 6    # WTP_PATH_HALF: a float16 tensor that got no transform (csrc/half.hip)
 
 
 def carried_level(tensors, wavelet, level, flatten=False):
@@ -284,6 +320,8 @@ def decode(results_dev, n):
         d = {k: r[k].item() for k in RESULT_DTYPE.names}
         d["thr32"] = float(np.array(d["thr32_bits"], np.uint32).view(np.float32))
         d["max_abs"] = np.array(d["max_abs_bits"], np.uint32).view(np.float32)[()]
+        if d["path"] == MODE_HALF:  # np.max of a float16 array
+            d["max_abs"] = np.float16(d["max_abs"])
         d["nonzero"] = d["numel"] - d["zero_count"]
         out.append(d)
     return out
