@@ -111,7 +111,7 @@ int self_check() {
     for (int trial = 0; trial < 60; ++trial) {
         const long long n = 1 + (long long)(next() % (trial < 30 ? 40 : 70000));
         std::vector<uint16_t> w(n), srt(n);
-        const uint32_t span = trial % 3 == 0 ? 0x40 : 0x7C00; // ties, or every finite key
+        const uint32_t span = trial % 3 == 0 ? 0x40 : (trial % 3 == 1 ? 0x7C00 : 0x8000); // ties, every finite key, or inf and NaN keys too
         for (auto& x : w) x = (uint16_t)((next() % span) | ((next() & 1) << 15));
         for (long long i = 0; i < n; ++i) srt[i] = (uint16_t)h16_key(w[i]);
         std::sort(srt.begin(), srt.end());

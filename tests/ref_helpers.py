@@ -1,5 +1,6 @@
 """References and constants that more than one GPU test file needs: the absolute-threshold
-method's yardstick and path ids (tests/test_gpu_abs_threshold.py, tests/test_gpu_special_values.py)
+method's yardstick and path ids (tests/test_gpu_abs_threshold.py, tests/test_gpu_special_values.py),
+the reference of a transformed float16 tensor (tests/test_special_values_ref.py and the GPU file),
 k_fwin's patch origins (tests/test_gpu_fused_select.py, tests/test_gpu_special_values.py), and
 np.percentile's ranks and the selection's key bins (tests/test_sweep_core.py,
 tests/test_select_host.py, tests/test_gpu_select_units.py)."""
@@ -18,6 +19,16 @@ def abs_oracle(x, wavelet, level, thr):
     if x.ndim < 2:
         return np.where(np.abs(x) < thr32, np.float32(0), x)
     return O.waverec2_packed(O.wavedec2_packed(x, wavelet, level), x.shape, wavelet, level, thr32)
+
+
+def f16_transformed_ref(x16, wavelet, level, pct):
+    """A float16 tensor that gets a transform (periodization): the oracle on the widened input,
+    narrowed once; returns (float32 result, float16 result, the oracle's record with the zeros
+    counted after the narrowing)."""
+    with np.errstate(all="ignore"):
+        out32, d = O.prune_tensor(x16.astype(np.float32), wavelet, level, pct)
+        out16 = out32.astype(np.float16)
+    return out32, out16, dict(d, zero_count=int((out16 == 0).sum()))
 
 
 def patch_origins(R, C):

@@ -90,17 +90,21 @@ def neg_zero_words(a):
     return int((np.ascontiguousarray(a, np.float32).view(np.uint32) == NEG_ZERO_BITS).sum())
 
 
+_WORD = {np.float16: np.uint16, np.float32: np.uint32, np.float64: np.uint64}
+
+
 def assert_same_bits(got, ref, tag=""):
-    """NaN masks identical; everywhere else the words are equal (float32 or float64, any shape)."""
+    """NaN masks identical; everywhere else the words are equal (float16, float32 or float64, any
+    shape)."""
     got, ref = np.ascontiguousarray(got), np.ascontiguousarray(ref)
-    assert got.dtype == ref.dtype and got.dtype in (np.float32, np.float64), (tag, got.dtype, ref.dtype)
+    assert got.dtype == ref.dtype and got.dtype.type in _WORD, (tag, got.dtype, ref.dtype)
     assert got.shape == ref.shape, (tag, got.shape, ref.shape)
     gn, rn = np.isnan(got), np.isnan(ref)
     if not np.array_equal(gn, rn):
         diff = np.argwhere(gn != rn)
         raise AssertionError("%r: NaN masks differ at %d cells (got %d NaN, want %d), first %s" % (
             tag, len(diff), int(gn.sum()), int(rn.sum()), tuple(diff[0])))
-    u = np.uint32 if got.dtype == np.float32 else np.uint64
+    u = _WORD[got.dtype.type]
     bad = (got.view(u) != ref.view(u)) & ~rn
     if bad.any():
         k = tuple(np.argwhere(bad)[0])
@@ -132,3 +136,31 @@ def assert_same_record(r, rr, tag=""):
     assert_same_bits(f32_from_bits(r["max_abs_bits"]), np.float32(rr["max_abs"]), (tag, "max_abs"))
     for f in ("zero_count", "eff_level", "coeff_numel"):
         assert r[f] == rr[f], (tag, f, r[f], rr[f])
+
+
+# ---- float16 weights that get a transform (widened, the float32 path, narrowed once) ----
+
+F16_NAMES = ["zero_blocks", "nan_interior", "nan_corner", "infs", "half_subnormal", "overflow"]
+F16_SEED, F16_PCT = 97, 61.8
+# (shape, wavelet, level), tensor id = position; the last is tiled.  tests/test_special_values_ref.py
+# shows that the two scales below do at each what the cases are named for.
+F16_SETTINGS = [((4, 3, 7, 7), "haar", 2), ((8, 4, 3, 3), "haar", 1), ((16, 40), "rbio2.2", 1),
+                ((1, 2, 161, 464), "db8", 2)]
+F16_SYMMETRIC = ((6, 5, 8, 8), "db2", 1)  # tensor id len(F16_SETTINGS), under the symmetric extension
+HALF_SUBNORMAL_SCALE = 2.0 ** -16  # sigma 0.05 x 2^-16 = 7.6e-7: 12.5 steps of the half subnormals' 2^-24
+OVERFLOW_MAX, OVERFLOW_SCALE = 60000.0, 2.0  # max |x| scaled to 2 x 60000, then clipped to +-60000
+HALF_TINY = 2.0 ** -14  # the smallest normal half
+
+
+def cases_f16(shape, seed, tid):
+    """{name: float16 array}: cases() narrowed to float16, the base scaled so that most inputs are
+    half subnormals, and the base scaled and clipped so that a share of the inputs sits at +-60000
+    (every input finite) and the pruned reconstruction overshoots the largest half in places"""
+    cs = cases(shape, seed, tid)
+    out = {name: cs[name].astype(np.float16) for name in F16_NAMES[:4]}
+    base = plain(shape, seed, tid)
+    out["half_subnormal"] = (base * np.float32(HALF_SUBNORMAL_SCALE)).astype(np.float16)
+    b64 = base.astype(np.float64) * (OVERFLOW_SCALE * OVERFLOW_MAX / np.abs(base.astype(np.float64)).max())
+    out["overflow"] = np.clip(b64, -OVERFLOW_MAX, OVERFLOW_MAX).astype(np.float32).astype(np.float16)
+    assert sorted(out) == sorted(F16_NAMES) and all(a.dtype == np.float16 and a.shape == tuple(shape) for a in out.values())
+    return out

@@ -5,7 +5,9 @@ float16 with NumPy's float16 percentile and compare; tensors that get one (kind 
 path and are narrowed once.  Shapes: 1, 2 and 37 weights, conv kernels the clamp leaves at level 0,
 all zeros, half of the values tied, 41 145 weights (odd, three blocks of vectors), populations over
 many binades, the transformed shapes of the modes fixtures, a result that underflows in the
-narrowing, and a mixed list with and without the level carry."""
+narrowing, and a mixed list with and without the level carry.  The last section feeds +-inf and
+NaN to the tensors that get no transform and holds them to the same NumPy rule restated in scalar
+steps (half_ref.kind_b_ref), which tests/test_half_core.py ties to the fixtures."""
 import contextlib
 import io
 import warnings
@@ -15,6 +17,7 @@ import pytest
 import torch
 
 from tests import half_ref as H
+from tests import special_values as SV
 from wavelettransforms_amd import workloads as W
 
 pytestmark = pytest.mark.gpu
@@ -249,3 +252,128 @@ def test_dtype_errors(eng):
         DN.multi_resolution_analysis([h], "haar", 1, 0.01)
     with pytest.raises(TypeError):
         eng.min_prune([h], 0.5)
+
+
+# ---- +-inf and NaN in tensors that get no transform, against half_ref.kind_b_ref ----
+
+SPECIAL_PCTS = [0.0, 50.0, 61.8, 100.0]
+BIG_N = 41145  # odd; at an odd element offset: 7 head words, three blocks of vectors, 2 tail words
+
+
+def _check_special(eng, words, o, r, pct, eff_level, tag):
+    """one kind-B tensor against the restated NumPy rule: words exactly, thr64, the compare value
+    and the maximum by special_values.assert_same_bits, counts and level exactly"""
+    ref = H.kind_b_ref(words, pct)
+    got = _words(o)
+    assert o.dtype == torch.float16 and np.array_equal(got, ref["out"]), (tag, np.flatnonzero(got != ref["out"])[:5])
+    SV.assert_same_bits(np.float64(r["thr64"]), ref["thr64"], (tag, "thr64"))
+    SV.assert_same_bits(SV.f32_from_bits(r["thr32_bits"]), ref["cmp"].astype(np.float32), (tag, "thr32"))
+    SV.assert_same_bits(SV.f32_from_bits(r["max_abs_bits"]), ref["max"].astype(np.float32), (tag, "max_abs"))
+    assert r["zero_count"] == ref["zero_count"], (tag, r["zero_count"], ref["zero_count"])
+    assert r["eff_level"] == eff_level and r["coeff_numel"] == r["numel"] == words.size, (tag, r)
+    assert r["path"] == eng.MODE_HALF, (tag, r)
+    return ref
+
+
+def _half_cuda(words, shape=None):
+    t = torch.from_numpy(np.array(words, np.uint16).view(np.float16)).cuda()
+    return t if shape is None else t.view(shape)
+
+
+@pytest.mark.parametrize("pct", SPECIAL_PCTS)
+def test_special_values_small_populations(eng, pct):
+    """every population of half_ref.special_populations at 1, 2, 3 and 37 weights in one call (more
+    than two tables), and (4, 4, 3, 3) under bior3.3 level 5, which the clamp leaves at level 0"""
+    pops = [(name, w) for name, w in H.special_populations() if len(w) <= 37]
+    assert len(pops) > 64 and {len(w) for _, w in pops} == {1, 2, 3, 37}
+    xs = [_half_cuda(w) for _, w in pops]
+    outs, recs = eng.prune(xs, "haar", 2, pct)
+    for (name, w), x, o, r in zip(pops, xs, outs, recs):
+        _check_special(eng, w, o, r, pct, 2, (name, pct))
+        assert np.array_equal(_words(x), w), (name, "input untouched")
+    b = H.base_words(144, 7)
+    r50, r618 = H.np_ranks(144, 50.0)[0] + 1, H.np_ranks(144, 61.8)[0] + 1
+    conv = [b, H.put(b, {71: H.SNAN}), H.infs_from_rank(b, 143), H.infs_from_rank(b, r50), H.infs_from_rank(b, r618),
+            H.put(H.infs_from_rank(b, 140), {0: H.NEG_QNAN}), H.infs_from_rank(b, 0), H.infs_from_rank(b, 1)]
+    xs = [_half_cuda(w, (4, 4, 3, 3)) for w in conv]
+    outs, recs = eng.prune(xs, "bior3.3", 5, pct)
+    for i, (w, o, r) in enumerate(zip(conv, outs, recs)):
+        ref = _check_special(eng, w, o, r, pct, 0, ("conv", i, pct))
+        assert list(o.shape) == [4, 4, 3, 3]
+        if (i, pct) in ((3, 50.0), (7, 0.0)) or (i in (2, 3, 4) and pct == 100.0):
+            assert np.isnan(ref["thr64"]), (i, pct)  # inf at rank lo + 1 at gamma 1/2 and 0; an infinite maximum
+        if (i, pct) == (4, 61.8):
+            assert ref["thr64"] == np.inf and ref["zero_count"] == r618, (i, pct)  # gamma 0.374
+
+
+def _big_cases():
+    """41 145 weights with one special word: element 0 (the scalar head of a tensor at an odd
+    element offset), a word of the middle block's vector body, the last word of the scalar tail"""
+    b = H.base_words(BIG_N, 11)
+    head, body, last = 0, 7 + 8 * (2048 + 1000) + 3, BIG_N - 1
+    cases = [b]
+    for pos in (head, body, last):
+        cases.append(H.put(b, {pos: [H.QNAN, H.SNAN, H.NEG_QNAN][len(cases) % 3]}))
+        cases.append(H.put(b, {pos: H.NEG_INF if pos == body else H.INF}))
+    return cases, (head, body, last)
+
+
+@pytest.mark.parametrize("in_place", [False, True])
+def test_special_values_in_head_body_and_tail(eng, in_place):
+    """a NaN or an inf that one workgroup's histogram alone sees (block 0 takes the head and the
+    tail, block 1 the middle vectors) reaches the tensor's maximum and threshold; out of place the
+    output's phase differs from the input's and the mask walks word by word, in place it stores
+    vectors"""
+    cases, (head, body, last) = _big_cases()
+    for pct in SPECIAL_PCTS:
+        bufs = [torch.zeros(BIG_N + 16, dtype=torch.float16, device="cuda") for _ in cases]
+        xs = []
+        for buf, w in zip(bufs, cases):
+            buf[1:1 + BIG_N] = _half_cuda(w)
+            xs.append(buf[1:1 + BIG_N])
+        assert all(x.data_ptr() % 16 == 2 for x in xs)
+        sp = 7 + 8 * ((BIG_N - 7) // 8)
+        assert (BIG_N - 7) // 8 > 2 * 16384 // 8 and sp <= last < BIG_N and 7 + 16384 <= body < 7 + 2 * 16384
+        outs, recs = eng.prune(xs, "haar", 2, pct, outs=xs if in_place else None)
+        for i, (w, x, o, r) in enumerate(zip(cases, xs, outs, recs)):
+            ref = _check_special(eng, w, o, r, pct, 2, (i, pct, in_place))
+            if in_place:
+                assert o.data_ptr() == x.data_ptr()
+            else:
+                assert o.data_ptr() % 16 != 2 and np.array_equal(_words(x), w), (i, "input untouched")
+            if i % 2 == 1:  # the NaN cases: the maximum and the threshold are NaN, nothing is pruned
+                assert np.isnan(ref["max"]) and np.isnan(ref["thr64"]) and np.array_equal(ref["out"], w), i
+            elif i:         # one inf: a finite threshold below the 100th percentile, NaN at it
+                assert np.isinf(ref["max"]) and np.isnan(ref["thr64"]) == (pct == 100.0), (i, pct)
+        for buf in bufs:
+            assert not bool(buf[0]) and not bool(buf[1 + BIG_N:].any()), "words outside the tensor were written"
+
+
+def _neighbours(eng, sizes, special, own, pct):
+    """one call of 1-D tensors of `sizes`, those of `special` {index: function of the base words}
+    holding special values: every tensor against the restated rule, those of `own` also against a
+    call of their own"""
+    ws = [H.base_words(n, 300 + i) for i, n in enumerate(sizes)]
+    for i, f in special.items():
+        ws[i] = f(ws[i])
+    xs = [_half_cuda(w) for w in ws]
+    outs, recs = eng.prune(xs, "haar", 2, pct, carry_level=False)
+    for i, (w, o, r) in enumerate(zip(ws, outs, recs)):
+        ref = _check_special(eng, w, o, r, pct, 2, (i, pct))
+        if i not in special:
+            assert np.isfinite(ref["thr64"]), i
+    for i in own:
+        assert i not in special
+        o1, r1 = eng.prune([xs[i]], "haar", 2, pct, carry_level=False)
+        assert np.array_equal(_words(outs[i]), _words(o1[0])) and recs[i] == r1[0], (i, pct, recs[i], r1[0])
+
+
+@pytest.mark.parametrize("pct", SPECIAL_PCTS)
+def test_special_tensors_leave_their_neighbours_alone(eng, pct):
+    """eight tensors, numbers 2 and 5 with a NaN and an inf; 70 tensors (three tables), numbers 31,
+    32 and 69 special: the ordinary ones come out as from a call of their own"""
+    nan_and_inf = lambda w: H.put(H.infs_from_rank(w, len(w) - 1), {len(w) // 2: H.QNAN})  # noqa: E731
+    top_inf = lambda w: H.infs_from_rank(w, len(w) - 1)  # noqa: E731
+    _neighbours(eng, [37, 2000, 500, 144, 1000, 37, 3, 20000], {2: nan_and_inf, 5: top_inf}, [0, 1, 3, 4, 6, 7], pct)
+    _neighbours(eng, [2 + i % 38 for i in range(70)], {31: nan_and_inf, 32: top_inf, 69: nan_and_inf},
+                [0, 30, 33, 63, 64, 68], pct)

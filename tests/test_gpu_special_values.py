@@ -20,6 +20,10 @@ packed coefficient may be -0.0 (pywt's sums start at +0), which is asserted on i
   abs       prune_abs: k_abs_tiny and the chain at unclamped levels
   modes     k_mtiny_* and k_mdwt_* / k_midwt_* under the five extension modes
   sweep     prune_sweep over transformed tensors
+  f16       float16 weights that get a transform: k_h16_widen, the float32 path, k_h16_narrow, with
+            half subnormals and results that overflow in the narrowing (special_values.cases_f16)
+  abs sweep prune_abs_sweep: k_abs_tiny_sweep, the sweep's chain and its mask path at an ordinary,
+            a subnormal, a zero, an infinite, a NaN and a 2^100 threshold in one call
 The percentile calls run with no_resident=True so that the multi-launch form named above runs (a
 call this small is otherwise one launch of k_small), and once more as dispatched by default."""
 import json
@@ -32,7 +36,7 @@ import torch
 from oracle import oracle as O
 from tests import golden_io as G
 from tests import special_values as SV
-from tests.ref_helpers import ABS_CHAIN as CHAIN, ABS_TINY as TINY, abs_oracle, patch_origins
+from tests.ref_helpers import ABS_CHAIN as CHAIN, ABS_TINY as TINY, abs_oracle, f16_transformed_ref, patch_origins
 
 pytestmark = pytest.mark.gpu
 
@@ -293,3 +297,151 @@ def test_sweep_over_transformed_tensors(eng, case):
             _check_out(got[k][t].cpu().numpy(), recs[k][t], ref, (case, p, t))
     for t, (x, x_np) in enumerate(zip(xs, xs_np)):
         _check_packed(eng, x, "haar", _ref(x_np, "haar", 2, 50.0), (case, t))
+
+
+# ---- float16 weights that get a transform ----
+
+def _f16_words(t):
+    return t.detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+
+
+def _f16_run(eng, x16, wavelet, level, mode):
+    x = torch.from_numpy(x16).cuda()
+    outs, (r,) = eng.prune([x], wavelet, level, SV.F16_PCT, carry_level=False, mode=mode)
+    assert outs[0].dtype == torch.float16 and r["path"] != eng.MODE_HALF and r["numel"] == x16.size
+    assert np.array_equal(_f16_words(x), x16.view(np.uint16)), "the input is untouched"
+    return _f16_words(outs[0]).view(np.float16), r
+
+
+@pytest.mark.parametrize("tid", range(len(SV.F16_SETTINGS)))
+def test_f16_transformed(eng, tid):
+    """k_h16_widen, the float32 path and k_h16_narrow on blocks of signed zeros, NaN, +-inf, half
+    subnormals in and out, and results that overflow in the narrowing: the oracle on the widened
+    input, narrowed once, with the zeros counted after the narrowing.  The sign of a zero counts:
+    a negative result below 2^-25 narrows to -0.0."""
+    shape, wavelet, level = SV.F16_SETTINGS[tid]
+    for name, x16 in SV.cases_f16(shape, SV.F16_SEED, tid).items():
+        _, ref16, rr = f16_transformed_ref(x16, wavelet, level, SV.F16_PCT)
+        assert rr["eff_level"] == level, (shape, name)
+        out, r = _f16_run(eng, x16, wavelet, level, "periodization")
+        SV.assert_same_bits(out, ref16, (shape, wavelet, name, "out"))
+        SV.assert_same_record(r, rr, (shape, wavelet, name))
+        assert r["zero_count"] == int((out.view(np.uint16) & 0x7FFF == 0).sum()), (shape, name)
+
+
+def test_f16_transformed_symmetric(eng):
+    """the same under one extension mode: the float32 result of the modes' reference chain
+    (tests/modes_ref.py, the host build of csrc/wt_modes_core.h), narrowed once"""
+    from tests import modes_ref
+    shape, wavelet, level = SV.F16_SYMMETRIC
+    for name, x16 in SV.cases_f16(shape, SV.F16_SEED, len(SV.F16_SETTINGS)).items():
+        with np.errstate(all="ignore"):
+            packed, thr64, thr32, max_abs, out32, eff = modes_ref.chain(x16.astype(np.float32), wavelet, level, "symmetric",
+                                                                      SV.F16_PCT)
+            ref16 = out32.astype(np.float16)
+        rr = dict(thr64=thr64, thr32=thr32, max_abs=max_abs, zero_count=int((ref16 == 0).sum()), eff_level=eff,
+                  coeff_numel=packed.size)
+        assert eff == level
+        out, r = _f16_run(eng, x16, wavelet, level, "symmetric")
+        SV.assert_same_bits(out, ref16, (name, "out"))
+        SV.assert_same_record(r, rr, name)
+
+
+# ---- absolute-threshold sweep ----
+
+SWEEP_THRS = [ABS_THR, ABS_THR_SUBNORMAL, 0.0, float("inf"), float("nan"), 2.0 ** 100]
+
+
+def _abs_refs(x_np, wavelet, level, thrs):
+    """abs_oracle at each threshold, the transform taken once"""
+    with np.errstate(all="ignore"):
+        if x_np.ndim < 2:
+            return [abs_oracle(x_np, wavelet, level, t) for t in thrs]
+        P = O.wavedec2_packed(x_np, wavelet, level)
+        return [O.waverec2_packed(P, x_np.shape, wavelet, level, np.float32(t)) for t in thrs]
+
+
+def _sweep_case(eng, x_np, wavelet, level, thrs, path, tag, against_call=True):
+    """one sweep of one tensor: every threshold's output and record against the oracle at that
+    threshold and against the ordinary call; returns the outputs"""
+    refs = _abs_refs(x_np, wavelet, level, thrs)
+    x = _dev(x_np)
+    outs, recs = eng.prune_abs_sweep([x], wavelet, level, thrs)
+    assert len(outs) == len(recs) == len(thrs)
+    assert np.array_equal(x.cpu().numpy().view(np.uint32), x_np.view(np.uint32)), "the input is untouched"
+    eff = level if x_np.ndim >= 2 else 0
+    cells = x_np.size
+    if x_np.ndim >= 2:
+        pr, pc = O.packed_shape(x_np.shape[-2], x_np.shape[-1], level)
+        cells = x_np.size // (x_np.shape[-2] * x_np.shape[-1]) * pr * pc
+    got = []
+    for k, (thr, ref) in enumerate(zip(thrs, refs)):
+        out, r = outs[k][0].cpu().numpy(), recs[k][0]
+        t = (tag, k, thr)
+        SV.assert_same_bits(out, ref, t)
+        if eff >= 1:
+            assert SV.neg_zero_words(out) == 0 and SV.neg_zero_words(ref) == 0, t
+        assert r["nonzero_in"] == int(np.count_nonzero(x_np)) and r["nonzero_out"] == int(np.count_nonzero(ref)), (t, r)
+        assert r["thr32_bits"] == G.f32_bits(thr) and r["path"] == path and r["level"] == eff, (t, r)
+        assert r["coeff_numel"] == cells and r["numel"] == x_np.size, (t, r)
+        if against_call:
+            o1, (r1,) = eng.prune_abs([x], wavelet, level, thr)
+            SV.assert_same_bits(out, o1[0].cpu().numpy(), (t, "the ordinary call"))
+            assert {f: v for f, v in r.items() if f != "thr32"} == {f: v for f, v in r1.items() if f != "thr32"}, t
+        got.append(out)
+    return got, refs
+
+
+@pytest.mark.parametrize("shape,wavelet,level,path", [
+    ((4, 3, 7, 7), "db2", 3, TINY), ((4, 3, 7, 7), "bior3.3", 5, TINY),
+    ((6, 1, 8, 8), "db2", 3, TINY), ((6, 1, 8, 8), "bior3.3", 5, TINY),
+    ((3, 2, 9, 9), "db2", 3, CHAIN), ((3, 2, 9, 9), "bior3.3", 5, CHAIN),
+    (SHAPE, "db8", 3, CHAIN)])
+def test_abs_sweep(eng, shape, wavelet, level, path):
+    """k_abs_tiny_sweep (the mask applied as a coefficient is read from the raw area) and the
+    sweep's chain at test_absolute_threshold's shapes: one sweep per case at an ordinary, a
+    subnormal, a zero, an infinite, a NaN and a 2^100 threshold, so that |c| < thr meets c NaN,
+    +-inf and subnormal under each"""
+    assert 0 < np.float32(ABS_THR_SUBNORMAL) < np.float32(2.0 ** -126)
+    cs = inputs(shape)
+    for name in ABS_CASES:
+        got, refs = _sweep_case(eng, cs[name], wavelet, level, SWEEP_THRS, path, (shape, wavelet, level, name))
+        if name in ("nan_corner", "infs"):
+            assert all(np.isnan(ref).any() for ref in refs), name
+        if name == "subnormal":  # on the oracle alone: the subnormal threshold zeroes some and not all coefficients
+            with np.errstate(all="ignore"):
+                P = O.wavedec2_packed(cs[name], wavelet, level)
+            assert 0.02 < float((np.abs(P) < np.float32(ABS_THR_SUBNORMAL)).mean()) < 0.98, (shape, wavelet, name)
+            assert not np.array_equal(refs[1], refs[2]), (shape, wavelet, name)
+
+
+@pytest.mark.parametrize("shape,level", [((3, 2, 9, 9), 0), ((64,), 5)])
+def test_abs_sweep_mask_path(eng, shape, level):
+    """level 0 and a 1-D tensor: the mask alone.  -0.0 survives a threshold of 0, NaN or -1 and
+    becomes +0 under every other; the reference says which."""
+    thrs = SWEEP_THRS + [-1.0]
+    for name in ABS_CASES:
+        x_np = inputs(shape)[name] if len(shape) > 1 else np.ascontiguousarray(inputs((8, 8))[name].reshape(-1))
+        got, refs = _sweep_case(eng, x_np, "bior3.3", level, thrs, 0, (shape, name))
+        if name == "zero_blocks":
+            nz = SV.neg_zero_words(x_np)
+            assert nz > 0 and [SV.neg_zero_words(r) for r in refs] == [0, 0, nz, 0, nz, 0, nz], (shape, name)
+            assert [SV.neg_zero_words(o) for o in got] == [0, 0, nz, 0, nz, 0, nz], (shape, name)
+
+
+def test_abs_sweep_tiny_list_longer_than_a_wave(eng):
+    """70 images of 3 x 3 under bior3.3 level 5, a NaN in image 69 (the partial last wave) and -inf
+    in image 5: every other image comes out as the same image of the plain input does -- a special
+    value in one lane's image does not reach another lane of the arena"""
+    shape = (70, 1, 3, 3)
+    plain = inputs(shape)["plain"]
+    x_np = np.array(plain)
+    x_np[69, 0, 1, 2] = np.nan
+    x_np[5, 0, 0, 1] = -np.inf
+    tag = (shape, "nan and -inf")
+    got, refs = _sweep_case(eng, x_np, "bior3.3", 5, SWEEP_THRS, TINY, tag)
+    got_plain, _ = _sweep_case(eng, plain, "bior3.3", 5, SWEEP_THRS, TINY, (shape, "plain"), against_call=False)
+    others = [i for i in range(70) if i not in (5, 69)]
+    for k in range(len(SWEEP_THRS)):
+        SV.assert_same_bits(got[k][others], got_plain[k][others], (tag, k, "the other images"))
+        assert np.isfinite(got[k][others]).all() and not np.isfinite(got[k][[5, 69]]).all(), (tag, k)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests import half_ref as H
+from tests import special_values as SV
 from wavelettransforms_amd import workloads as W
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -258,3 +259,146 @@ def test_split_of_an_unaligned_tensor(core):
                 assert (addr + 2 * h.value) % 16 == 0
             if h.value < n and h.value:
                 assert (addr + 2 * h.value) % 16 == 0
+
+
+# ---- the rule restated in NumPy scalars (half_ref.kind_b_ref), and special values ----
+
+def _half_word(w):
+    return np.array(w, np.uint16).view(np.float16)
+
+
+def test_restated_rule_reproduces_every_stored_kind_b_result():
+    """half_ref.kind_b_ref against the NumPy 1.26.4 run that made the fixtures: thr64, the compare
+    value, the maximum, the zero count and the output words (stored, or their hash) of every
+    kind-B tensor of the fixture calls and of the whole wide group."""
+    n = 0
+    for key, ti, call, rec in kind_b_records():
+        x = H.make_input(rec, W.synth_numpy)
+        ref = H.kind_b_ref(x.view(np.uint16), call["pct"])
+        assert float(ref["thr64"]).hex() == rec["thr64_hex"], (key, ti)
+        assert int(ref["cmp"].astype(np.float32).view(np.uint32)) == rec["cmp_bits"], (key, ti)
+        assert int(ref["max"].astype(np.float32).view(np.uint32)) == rec["max_bits"], (key, ti)
+        assert ref["zero_count"] == rec["zero_count"], (key, ti)
+        assert H.words_hash(ref["out"].view(np.float16)) == rec["out_hash"], (key, ti)
+        stored = H.arrays().get("%s/%d" % (key, ti))
+        if stored is not None:
+            assert np.array_equal(stored.view(np.uint16).reshape(-1), ref["out"]), (key, ti)
+        n += 1
+    assert n == 51
+    wide = H.manifest()["wide"]
+    words = H.arrays()["wide/words"]
+    assert len(wide) == 156
+    for c in wide:
+        ref = H.kind_b_ref(words[c["offset"]:c["offset"] + c["n"]], c["pct"])
+        assert float(ref["thr64"]).hex() == c["thr64_hex"], c
+        assert int(ref["cmp"].astype(np.float32).view(np.uint32)) == c["cmp_bits"], c
+        assert int(ref["max"].astype(np.float32).view(np.uint32)) == c["max_bits"], c
+        assert ref["zero_count"] == c["zero_count"], c
+        assert np.array_equal(ref["out"], words[c["offset"] + c["n"]:c["offset"] + 2 * c["n"]]), c
+
+
+@pytest.fixture(scope="module")
+def special():
+    """[(name, pct, words, reference)] of half_ref.special_populations at half_ref.SPECIAL_PCTS"""
+    return [(name, pct, w, H.kind_b_ref(w, pct)) for name, w in H.special_populations() for pct in H.SPECIAL_PCTS]
+
+
+def test_special_populations_are_what_they_are_named(special):
+    """On the reference alone: a NaN leaves the tensor as it is, infs above the ranks leave a finite
+    threshold that prunes some and not all, an inf at rank lo + 1 over a finite rank lo gives NaN
+    at gamma 0, inf below one half and NaN from one half on, and -0.0 and subnormals are there."""
+    branches = {"zero": 0, "below_half": 0, "from_half": 0}
+    n_nan = n_above = n_both = n_top_inf = 0
+    for name, pct, w, ref in special:
+        n = len(w)
+        keys = np.sort(w & np.uint16(0x7FFF))
+        lo, above, g = H.np_ranks(n, pct)
+        tag = (name, pct)
+        if keys[-1] >= H.NAN_KEY_MIN:
+            assert np.isnan(ref["thr64"]) and np.isnan(ref["cmp"]) and np.isnan(ref["max"]), tag
+            assert np.array_equal(ref["out"], w), tag
+            n_nan += 1
+            continue
+        assert not np.isnan(ref["max"]), tag
+        if name.startswith("inf_above") and 0 < pct < 100:
+            assert not above and keys[lo + 1] < H.INF == keys[-1], tag
+            assert np.isfinite(ref["thr64"]), tag
+            pruned = int((ref["out"] != w).sum())
+            assert 0 < pruned < n, tag
+            assert np.array_equal(ref["out"][(w & 0x7FFF) == H.INF], w[(w & 0x7FFF) == H.INF]), tag
+            n_above += 1
+        if above and keys[-1] == H.INF:  # the percentile is an infinite maximum: inf - inf
+            assert np.isnan(ref["thr64"]) and np.array_equal(ref["out"], w), tag
+            n_top_inf += 1
+        if not above and keys[lo] < H.INF == keys[lo + 1]:
+            if g == 0:
+                assert np.isnan(ref["thr64"]) and np.array_equal(ref["out"], w), tag
+                branches["zero"] += 1
+            elif g < 0.5:
+                assert ref["thr64"] == np.inf and ref["cmp"] == np.inf, tag
+                finite = (w & 0x7FFF) < H.INF
+                assert not ref["out"][finite].any() and np.array_equal(ref["out"][~finite], w[~finite]), tag
+                branches["below_half"] += 1
+            else:
+                assert np.isnan(ref["thr64"]) and np.array_equal(ref["out"], w), tag
+                branches["from_half"] += 1
+        if not above and keys[lo] == H.INF:
+            assert np.isnan(ref["thr64"]), tag
+            n_both += 1
+    assert min(branches.values()) >= 2, branches
+    assert n_nan >= 5 * 10 * 6 and n_above == 2 * 2 * 4 and n_both >= 10 and n_top_inf >= 10
+    by_name = {name: w for name, _, w, _ in special}
+    assert int((by_name["neg_zero_block_2000"] == H.NEG_ZERO).sum()) == 666
+    assert all(0 < (k & 0x7FFF) < 0x400 for k in by_name["subnormal_37"])
+    # -0.0 under a threshold of 0 keeps its sign; a pruned word is +0 and both count as zeros
+    ref = [r for name, pct, _, r in special if name == "neg_zero_block_2000" and pct == 23.6][0]
+    assert ref["thr64"] == 0.0 and int((ref["out"] == H.NEG_ZERO).sum()) == 666 and ref["zero_count"] == 668
+    ref = [r for name, pct, _, r in special if name == "neg_zero_block_2000" and pct == 90.0][0]
+    assert not (ref["out"] == H.NEG_ZERO).any() and ref["zero_count"] > 1000
+
+
+def _assert_special(tag, ref, out, thr, ck, mk, z, cmp_word):
+    """one result of the core against the restated rule: words exactly, thr64, the compare value
+    and the maximum by NaN-ness first and bits otherwise"""
+    assert np.array_equal(out, ref["out"]), (tag, np.flatnonzero(out != ref["out"])[:5])
+    SV.assert_same_bits(np.float64(thr), ref["thr64"], (tag, "thr64"))
+    SV.assert_same_bits(_half_word(cmp_word), ref["cmp"], (tag, "compare value"))
+    SV.assert_same_bits(_half_word(mk), ref["max"], (tag, "max"))
+    # the key the mask compares with: the compare value's, 0 (nothing is below it) when it is NaN
+    assert ck == (0 if np.isnan(ref["cmp"]) else int(ref["cmp"].view(np.uint16))), tag
+    assert z == ref["zero_count"], tag
+
+
+def test_special_populations_through_the_core(core, special):
+    core.half_core_from_double.argtypes = [ctypes.c_double]
+    core.half_core_from_double.restype = ctypes.c_uint16
+    for name, pct, w, ref in special:
+        out, thr, ck, mk, z = prune(core, w, pct)
+        _assert_special((name, pct), ref, out, thr, ck, mk, z, core.half_core_from_double(thr))
+
+
+def _special_program_lines(exe, special):
+    lines = []
+    for name, pct, w, ref in special:
+        r0, above, gamma = H.np_ranks(len(w), pct)
+        lines.append("%d %d %d %s %s" % (len(w), r0, above, float(gamma).hex(), " ".join(str(int(v)) for v in w)))
+    out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout[-400:] + out.stderr[-2000:]
+    got = out.stdout.strip().split("\n")
+    assert len(got) == len(special)
+    for (name, pct, w, ref), line in zip(special, got):
+        f = line.split()
+        thr = float.fromhex(f[0])
+        with np.errstate(over="ignore"):
+            cmp_word = int(np.float64(thr).astype(np.float16).view(np.uint16))  # the program prints the key alone
+        _assert_special((name, pct), ref, np.array([int(v) for v in f[4:]], np.uint16), thr, int(f[1]), int(f[2]),
+                        int(f[3]), cmp_word)
+
+
+def test_special_populations_through_the_program(special):
+    _special_program_lines(_build(EXE, ["-O2"]), special)
+
+
+def test_special_populations_through_the_program_under_asan_ubsan(special):
+    """the stand-alone sanitizer build of test_program_under_asan_ubsan on the special populations"""
+    _special_program_lines(_build(EXE_SAN, SAN), special)

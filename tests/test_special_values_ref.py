@@ -265,3 +265,52 @@ def test_generator_gives_the_committed_modes_fixture():
     # under the zero extension an inf never meets its negative: a finite threshold beside inf coefficients
     assert any(c["case"] == "infs" and c["thr64_hex"] != "nan" for c in cases.values())
     assert any(c["case"] == "infs" and c["packed_nan"] for c in cases.values())
+
+
+def test_float16_cases_are_not_trivial():
+    """special_values.cases_f16 at the settings tests/test_gpu_special_values.py runs them, on the
+    oracle alone (and the modes' reference chain for the symmetric setting): `overflow` holds finite
+    inputs only and narrows at least one finite float32 result to inf; `half_subnormal` is mostly
+    half subnormals, at least one nonzero float32 result below 2^-25 narrows to a signed zero and
+    at least one result to a subnormal; a NaN or an inf in the input reaches the narrowed result.
+    Figures at the time of writing: overflow 16 / 2 / 15 / 2620 results narrowed to inf at the four
+    settings, half_subnormal 30 / 1 / 32 / 6760 narrowed to zero (21 / 1 / 22 / 3400 of them -0.0)."""
+    from tests import modes_ref
+    from tests.ref_helpers import f16_transformed_ref
+    settings = [(s, w, lv, "periodization") for s, w, lv in SV.F16_SETTINGS] + [SV.F16_SYMMETRIC + ("symmetric",)]
+    for tid, (shape, wavelet, level, mode) in enumerate(settings):
+        cs = SV.cases_f16(shape, SV.F16_SEED, tid)
+        res = {}
+        for name, x16 in cs.items():
+            if mode == "periodization":
+                out32, out16, d = f16_transformed_ref(x16, wavelet, level, SV.F16_PCT)
+                assert d["eff_level"] == level, (shape, name)
+            else:
+                with np.errstate(all="ignore"):
+                    out32 = modes_ref.chain(x16.astype(np.float32), wavelet, level, mode, SV.F16_PCT)[4]
+                    out16 = out32.astype(np.float16)
+            res[name] = (out32, out16)
+        tag = (shape, wavelet)
+        x16 = cs["overflow"]
+        assert np.isfinite(x16).all() and np.abs(x16).max() == np.float16(SV.OVERFLOW_MAX), tag
+        out32, out16 = res["overflow"]
+        assert int((np.isfinite(out32) & np.isinf(out16)).sum()) >= 1 and np.isfinite(out32).all(), tag
+        x16 = cs["half_subnormal"]
+        assert int(((np.abs(x16) < SV.HALF_TINY) & (x16 != 0)).sum()) > 0.9 * x16.size, tag
+        out32, out16 = res["half_subnormal"]
+        assert int(((out32 != 0) & (np.abs(out32) < 2.0 ** -25) & (out16 == 0)).sum()) >= 1, tag
+        assert int(((out16 != 0) & (np.abs(out16) < SV.HALF_TINY)).sum()) >= 1, tag
+        for name in ("nan_interior", "nan_corner", "infs"):
+            assert not np.isfinite(cs[name]).all() and 1 <= int(np.isnan(res[name][1]).sum()) <= x16.size // 2, (tag, name)
+        x16 = cs["zero_blocks"]
+        assert int((x16.view(np.uint16) == 0x8000).sum()) > 0 and np.isfinite(res["zero_blocks"][1]).all(), tag
+
+
+def test_the_comparison_rule_on_halves():
+    """assert_same_bits on float16 words: the same rule at 16 bits"""
+    f16 = lambda *bits: np.array(bits, np.uint16).view(np.float16)  # noqa: E731
+    SV.assert_same_bits(f16(0x7E00, 0, 0x8000, 0x3C00, 0x7C00), f16(0xFE01, 0, 0x8000, 0x3C00, 0x7C00))
+    for got, ref in ((f16(0x8000), f16(0)), (f16(0x7E00), f16(0x7C00)), (f16(0x3C00), f16(0x3C01)), (f16(1), f16(0)),
+                     (f16(0x3C00), np.float32(1.0))):
+        with pytest.raises(AssertionError):
+            SV.assert_same_bits(got, ref, "must differ")

@@ -15,10 +15,12 @@
  *   convert  h16_to_float (exact), h16_from_double / h16_from_float (round to nearest even, once;
  *            subnormals, overflow to inf, NaN kept quiet).
  *
- * Not pinned: |w| >= 65000, +-inf and NaN in the input (the compare's type changes there, or the
- * threshold is NaN).  The code is safe on them -- a key is always a valid bin -- but no parity
- * with the reference is claimed.  Shared by half.hip and tests/native/halfcore.cpp.  Build with
- * -ffp-contract=off: the blend is a separate multiply and add.
+ * Pinned on +-inf and NaN in the input as well (tests/half_ref.kind_b_ref): a NaN makes the
+ * threshold NaN and nothing is pruned; an inf at a rank goes through the same difference and blend
+ * (inf - inf is NaN).  Not pinned: finite |w| >= 65000 (the compare's type changes there).  The
+ * code is safe on them -- a key is always a valid bin -- but no parity with the reference is
+ * claimed.  Shared by half.hip and tests/native/halfcore.cpp.  Build with -ffp-contract=off: the
+ * blend is a separate multiply and add.
  */
 #ifndef WT_HALF_CORE_H
 #define WT_HALF_CORE_H
@@ -116,18 +118,17 @@ WT_CORE uint16_t h16_diff(uint32_t ka, uint32_t kb) {
 }
 
 /* np.percentile of |w| over a float16 population from its order statistics ka <= kb (keys), gamma
- * and `above` (the percentile is the maximum, kmax).  Returns the key of half(thr64): the value
- * the float16 compare uses. */
+ * and `above` (the percentile is the maximum, kmax: NumPy takes a = b = max and gamma = n, so an
+ * infinite maximum gives d = inf - inf and a NaN threshold).  A NaN anywhere in the population
+ * (kmax above inf's key) makes the percentile NaN.  Returns the key of half(thr64): the value the
+ * float16 compare uses. */
 WT_CORE uint32_t h16_threshold(uint32_t ka, uint32_t kb, uint32_t kmax, double gamma, int above, double* thr64) {
-    double thr;
-    if (above) {
-        thr = (double)h16_to_float((uint16_t)kmax);
-    } else {
-        const double a = (double)h16_to_float((uint16_t)ka), b = (double)h16_to_float((uint16_t)kb);
-        const double d = (double)h16_to_float(h16_diff(ka, kb));
-        const double da = d * (1.0 - gamma), db = d * gamma;
-        thr = (gamma >= 0.5) ? b - da : a + db;
-    }
+    if (above) ka = kb = kmax;
+    const double a = (double)h16_to_float((uint16_t)ka), b = (double)h16_to_float((uint16_t)kb);
+    const double d = (double)h16_to_float(h16_diff(ka, kb));
+    const double da = d * (1.0 - gamma), db = d * gamma;
+    double thr = (gamma >= 0.5) ? b - da : a + db;
+    if (kmax > 0x7C00u) thr = (double)__builtin_nanf("");
     *thr64 = thr;
     const uint32_t ck = h16_key(h16_from_double(thr));
     return ck > 0x7C00u ? 0u : ck; /* a NaN threshold compares false with everything: nothing is pruned */
