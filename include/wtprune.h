@@ -22,6 +22,8 @@
  *                                   main_pruning.py:186 over its thresholds, in one call
  *   wtp_prune_abs_sweep_f32         multi_resolution_analysis of dwt_pruning_NoEntropy.py:29-60 at a
  *                                   grid of absolute thresholds (the same loop), in one call
+ *   wtp_prune_global_f32            (no reference counterpart: multi_resolution_analysis's transform and
+ *                                   compare with ONE percentile threshold over all tensors' coefficients)
  *   wtp_prune_f16                   multi_resolution_analysis on float16 weights (model.half())
  *   wtp_synth_f32                   (test/bench input generator, no reference counterpart)
  */
@@ -73,6 +75,7 @@ typedef struct wtp_result {
                                + 8 (9, 10, 11): the fused selection's patch window missed the ranks
                                and the segment was selected again over its coefficients;
                                5 a sweep's record; 6 a float16 tensor that got no transform (wtp_prune_f16);
+                               7 a global percentile's record (wtp_prune_global_f32);
                                99 = the resident launch's grid was not co-resident (results invalid) */
 } wtp_result;
 
@@ -287,6 +290,47 @@ int wtp_prune_sweep_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id,
                         const double* pcts /* host */, int npct, int flags,
                         float* const* outs /* host array of npct * ntensors device pointers */, void* workspace,
                         size_t workspace_bytes, wtp_result* results_dev /* npct * ntensors */, wtp_stream_t stream);
+
+/* ---- the global percentile: one threshold over the whole list (global magnitude pruning in the
+ * wavelet domain; an addition, the reference prunes per tensor) ----
+ * The level clamp, its carry (flags & WTP_CARRY_LEVEL) and the ndim < 2 branch are those of the
+ * sweep.  A tensor that gets a transform (ndim >= 2 and a clamped level >= 1) contributes its whole
+ * packed coefficient array, coeffs_to_array(wavedec2(...)) under periodization with the padding
+ * zeros of a packing that is not tight, exactly its population in the per-tensor entries; every
+ * other tensor contributes its raw values.  The POOL is the concatenation, N keys |x|.  For every
+ * k < npct: thr64 is NumPy 1.x's linear percentile pcts[k] of the pool (the two order statistics
+ * of rank (N - 1) pcts[k] / 100, their difference in float32, the blend in float64, from the upper
+ * end when gamma >= 0.5, NaN if the pool holds a NaN), thr32 = float32(thr64), and every tensor's
+ * output outs[k * ntensors + t] is where(|c| < thr32, +0, c) in float32, through waverec2 and its
+ * crop for a transformed tensor.  The per-tensor entries and this one share everything but the
+ * population: the forward transform runs once, one exact selection (three histogram passes over
+ * the pool whatever npct is, one shared state and one set of histograms for every tensor) finds
+ * all order statistics, every percentile's mask or inverse reads the pool's threshold.
+ * Records results_dev[k * ntensors + t] (percentile-major, as the sweep's): numel, coeff_numel,
+ * eff_level and zero_count are tensor t's own; thr64, thr32_bits and max_abs_bits are the pool's,
+ * the same in every record of percentile k (the maximum is the pool's because the thresholded
+ * array is the pool); path = WTP_PATH_GLOBAL.
+ * Arguments, flags (WTP_CARRY_LEVEL, WTP_SWEEP_THRESHOLDS_ONLY; any other bit is WTP_EARG), the
+ * output layout, the in-place rule (at most one output of a tensor may be its input), validation
+ * order and error codes are wtp_prune_sweep_f32's, and one more: a pool of more than 2^32 - 1 keys
+ * is WTP_EARG with a message naming the count (ranks, residuals and bins are 32 bits wide, and one
+ * bin may hold the whole pool).
+ * An empty pool is answered as the sweep answers the same list: ntensors == 0 is WTP_OK with nothing
+ * written (after the percentile check: a bad percentile is WTP_EBADPCT even then), and a list
+ * with an empty tensor is WTP_EEMPTY at that tensor -- the reference's percentile of an empty
+ * array -- so a call that reaches the device never has an empty pool.
+ * Workspace: wtp_global_workspace_size bytes (0 if the request is invalid, an over-full pool
+ * included).  Like the sweep's it needs no initialisation and is plain scratch of this entry
+ * alone: it MUST NOT be the workspace of wtp_prune*_f32 / wtp_threshold_f32 / wtp_min_prune_f32.
+ * Stream-ordered on the caller's stream only, no allocation, no copy from host memory, no
+ * synchronisation, capturable. */
+#define WTP_PATH_GLOBAL 7
+size_t wtp_global_workspace_size(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level, int npct,
+                                 int flags);
+int wtp_prune_global_f32(const wtp_tensor* tensors, int ntensors, int wavelet_id, int level,
+                         const double* pcts /* host */, int npct, int flags,
+                         float* const* outs /* host array of npct * ntensors device pointers */, void* workspace,
+                         size_t workspace_bytes, wtp_result* results_dev /* npct * ntensors */, wtp_stream_t stream);
 
 /* ---- float16 weights: multi_resolution_analysis on the tensors of model.half() ----
  * The reference takes float16 weights as they come (dwt_pruning.py:56 .numpy(), :61 / :84 rebuild

@@ -94,6 +94,9 @@ def lib():
             "wtp_sweep_workspace_size": ([tp, i32, i32, i32, i32, i32], sz),
             "wtp_prune_sweep_f32": ([tp, i32, i32, i32, ctypes.POINTER(f64), i32, i32, ctypes.POINTER(vp), vp, sz, vp,
                                      vp], i32),
+            "wtp_global_workspace_size": ([tp, i32, i32, i32, i32, i32], sz),
+            "wtp_prune_global_f32": ([tp, i32, i32, i32, ctypes.POINTER(f64), i32, i32, ctypes.POINTER(vp), vp, sz, vp,
+                                      vp], i32),
             "wtp_threshold_f32": ([vp, vp, i64, f64, vp, sz, vp, vp], i32),
             "wtp_dwt_workspace_size": ([i64, i64, i64, i32], sz),
             "wtp_wavedec2_f32": ([vp, vp, i64, i64, i64, i32, i32, vp, sz, vp], i32),

@@ -20,7 +20,7 @@ OUT_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(OUT_DIR, "libwtprune.so")
 SOURCES = ["prune_unit.hip", "filterbank.hip", "small.hip", "abs.hip", "modes.hip", "sweep.hip",
            "host_plan.hip", "host_chains.hip", "host_prune.hip", "host_methods.hip", "host_query.hip",
-           "host_sweep.hip", "half.hip", "host_half.hip"]
+           "host_sweep.hip", "half.hip", "host_half.hip", "global.hip", "host_global.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("WTP_OFFLOAD_ARCH", "gfx950")
 

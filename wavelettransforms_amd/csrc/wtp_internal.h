@@ -11,6 +11,7 @@
 #include "wt_abs_core.h"
 #include "wt_modes_core.h"
 #include "wt_sweep_core.h"
+#include "wt_global_core.h"
 
 #pragma clang fp contract(off)
 
@@ -617,6 +618,51 @@ void launch_sweep_init(uint32_t* words, int64_t nwords, hipStream_t s);
  * writes the records (zero_count = 0) and the threshold words */
 void launch_sweep_pass(const SwTable& t, int pass, const SwWs& w, wtp_result* res, hipStream_t s);
 void launch_sweep_mask(const SwMaskTable& t, const float* thr, wtp_result* res, hipStream_t s);
+/* ---- the global percentile (global.hip, wtp_prune_global_f32; index arithmetic: wt_global_core.h
+ * over wt_sweep_core.h) ----
+ * The sweep's selection over ONE population, the pool of every tensor's keys: one SwState, one
+ * pass-1 histogram and one set of slot histograms for each of the passes 2 and 3, which the
+ * workgroups of every launch group add into; one scan workgroup per pass. */
+struct GlSeg {
+    const float* data; /* the tensor's part of the pool: its input, or its packed array */
+    int64_t n;
+};
+struct GlTable { /* one launch group's populations */
+    int32_t nseg, nblk;
+    int32_t cpb;       /* chunks per workgroup */
+    int32_t pad;
+    int32_t blk_begin[SEG_PER_LAUNCH]; /* INT32_MAX past nseg */
+    GlSeg s[SEG_PER_LAUNCH];
+};
+struct GlRanks { /* seg_ranks of the pooled count, per percentile */
+    int32_t npct;
+    uint32_t above;    /* bit k: percentile k's two order statistics are both the maximum */
+    uint32_t r0[SW_MAX_PCT];
+    double gamma[SW_MAX_PCT];
+};
+struct GlRecSeg { /* what a record holds of its own tensor */
+    int64_t numel, coeff_numel;
+    int32_t eff_level, pad;
+};
+struct GlRecTable { /* one launch group's tensors t0 .. t0 + nseg of the call's ntensors */
+    int32_t nseg, t0, ntensors, npct;
+    GlRecSeg s[SEG_PER_LAUNCH];
+};
+struct GlWs { /* the pool's selection state in the workspace */
+    SwState* st;    /* one */
+    uint32_t* h1;   /* SW_BINS1 words */
+    uint32_t* h2;   /* SW_SLOT_WORDS words */
+    uint32_t* h3;   /* " */
+    float* thr;     /* npct float32 thresholds: the words the inverse transforms read */
+    double* thr64;  /* npct */
+    float* thr_tab; /* thr[k] at k * ntensors + t, the table k_sweep_mask indexes (k_global_records) */
+};
+/* pass 1..3 over one launch group's part of the pool */
+void launch_global_pass(const GlTable& t, int pass, const GlWs& w, hipStream_t s);
+/* the pass's scan, after every group's pass launch: one workgroup; the third writes thr and thr64 */
+void launch_global_scan(const GlRanks& r, int pass, const GlWs& w, hipStream_t s);
+/* after the third scan: a launch group's npct x nseg records (zero_count = 0) and its part of thr_tab */
+void launch_global_records(const GlRecTable& t, const GlWs& w, wtp_result* res, hipStream_t s);
 
 /* 1-D flattened mode (one line per tensor) */
 void launch_dwt1_level(const float* x, int64_t N, const Taps& tp, float* a, float* d, hipStream_t s);

@@ -21,7 +21,8 @@ float16 weights (model.half()) go through multi_resolution_analysis, prune_layer
 wavelet_pruning as they do through the reference, and come back as float16: a tensor that gets a
 transform is computed in float32 and narrowed once, one that gets none stays in float16 with
 NumPy's float16 percentile and compare (wtp_prune_f16).  All tensors of a call share one dtype.
-multi_resolution_analysis_sweep, flatten=True and percentile_based_thresholding take float32 only.
+multi_resolution_analysis_sweep, multi_resolution_analysis_global, flatten=True and
+percentile_based_thresholding take float32 only.
 """
 import os
 from typing import List, Tuple
@@ -36,7 +37,8 @@ from .utils import (append_to_experiment_log, check_and_set_pruned_instance_path
                     save_model, setup_csv_writer)
 
 __all__ = ["calculate_max_level", "analyze_pruning", "percentile_based_thresholding",
-           "multi_resolution_analysis", "multi_resolution_analysis_sweep", "prune_layer_weights", "wavelet_pruning",
+           "multi_resolution_analysis", "multi_resolution_analysis_sweep", "multi_resolution_analysis_global",
+           "prune_layer_weights", "wavelet_pruning",
            "prune_conv_layer", "apply_dwt_pruning"]
 
 
@@ -154,6 +156,34 @@ def multi_resolution_analysis_sweep(weights: List[torch.Tensor], wavelet: str, l
         dev_w = [_cuda(w.detach()) for w in weights]
         for i in range(0, len(percentiles), engine.WTP_SWEEP_MAX_PCT):
             outs, recs = engine.prune_sweep(dev_w, wavelet, level, percentiles[i:i + engine.WTP_SWEEP_MAX_PCT])
+            for o, r in zip(outs, recs):
+                if _mismatches(weights, r) > 0:
+                    print(f"Warning: Shape mismatch occurred in {_mismatches(weights, r)} weights")
+                pruned = [y.to(d).to(dtype=w.dtype).view(w.shape) for y, d, w in zip(o, devs, weights)]
+                result.append((pruned, int(sum(x["zero_count"] for x in r))))
+    return result
+
+
+def multi_resolution_analysis_global(weights: List[torch.Tensor], wavelet: str, level: int,
+                                     percentiles) -> List[Tuple[List[torch.Tensor], int]]:
+    """Global magnitude pruning in the wavelet domain (an addition; the reference prunes per
+    tensor): multi_resolution_analysis's transform, level carry and compare, with ONE threshold per
+    percentile for the whole list -- the percentile of the pooled |coefficients| of every tensor
+    (a tensor that gets no transform contributes its raw values), so the sparsity goes to the
+    tensors whose coefficients are small.  Returns a list over `percentiles` of (pruned tensors on
+    their original devices, total zero count).  float32 weights only; one device call for up to
+    engine.WTP_SWEEP_MAX_PCT percentiles (engine.prune_global), longer grids run in several.  No
+    threshold lines are printed."""
+    percentiles = list(percentiles)
+    if len(weights) == 0:
+        return [([], 0) for _ in percentiles]
+    weights = list(weights)
+    result = []
+    with torch.no_grad():
+        devs = [w.device for w in weights]
+        dev_w = [_cuda(w.detach()) for w in weights]
+        for i in range(0, len(percentiles), engine.WTP_SWEEP_MAX_PCT):
+            outs, recs = engine.prune_global(dev_w, wavelet, level, percentiles[i:i + engine.WTP_SWEEP_MAX_PCT])
             for o, r in zip(outs, recs):
                 if _mismatches(weights, r) > 0:
                     print(f"Warning: Shape mismatch occurred in {_mismatches(weights, r)} weights")

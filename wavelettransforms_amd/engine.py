@@ -31,7 +31,7 @@ def workspace(device, nbytes, stream=None, kind=None):
     ever used keeps its workspace (at the largest size it needed: a cfg5-sized call holds the
     packed coefficients of its images) until release_workspaces() drops it.  kind=None is the
     workspace of the selection entries, whose state the library keeps clean; an entry that uses its
-    workspace as plain scratch (launch_abs and launch_abs_sweep: kind="abs", launch_sweep: kind="sweep") gets one of its
+    workspace as plain scratch (launch_abs and launch_abs_sweep: kind="abs", launch_sweep: kind="sweep", launch_global: kind="global") gets one of its
     own, so it never writes over that state."""
     device = torch.device(device)
     if device.index is None:
@@ -552,6 +552,52 @@ def prune_sweep(tensors, wavelet, level, pcts, outs=None, carry_level=True, thre
     pcts = list(pcts)
     outs, res = launch_sweep(tensors, wavelet, level, pcts, outs=outs, carry_level=carry_level,
                              thresholds_only=thresholds_only)
+    return outs, _decode_blocks(res, len(pcts), len(tensors), N.RESULT_BYTES, decode)
+
+
+MODE_GLOBAL = 7  # include/wtprune.h: WTP_PATH_GLOBAL
+
+
+def launch_global(tensors, wavelet, level, pcts, outs=None, carry_level=True, thresholds_only=False, stream=None):
+    """Enqueue the global percentile (wtp_prune_global_f32) for `tensors` (CUDA float32) on `stream`
+    (default: the current stream): one forward transform, then ONE threshold per percentile for
+    the whole list -- the percentile of the pooled magnitudes of every tensor's coefficients (a
+    tensor that gets no transform contributes its raw values) -- and each percentile's mask or
+    inverse with it.  Returns (outs, results_dev) without synchronising, shaped as launch_sweep's:
+    outs[k][t] is tensor t pruned at the pool's pcts[k]-th percentile, block k of results_dev holds
+    len(tensors) wtp_result records with path == MODE_GLOBAL, whose thr64, thr32 and max_abs are
+    the pool's (equal in every record of the block) and whose other fields are the tensor's own.
+    At most eight percentiles; they may repeat and need not be sorted.  outs: a list over the
+    percentiles of output lists; at most one output of a tensor may be the tensor itself.
+    thresholds_only=True stops after the selection: outs is None, zero_count 0."""
+    pcts = [float(p) for p in pcts]
+    npct = len(pcts)
+    tensors, outs, n, device, desc = _prepare(tensors, outs, npct, "percentiles", no_outs=thresholds_only)
+    if n == 0:
+        return outs, None
+    L = N.lib()
+    wid = wavelet_id(wavelet)
+    flags = (WTP_CARRY_LEVEL if carry_level else 0) | (WTP_SWEEP_THRESHOLDS_ONLY if thresholds_only else 0)
+    stream = _current(device, stream)
+    nbytes = L.wtp_global_workspace_size(desc, n, wid, int(level), npct, flags)
+    # scratch of this entry alone: never the selection entries' workspace (include/wtprune.h)
+    ws = workspace(device, nbytes if nbytes else 256, stream, kind="global")
+    res = _results(max(1, npct) * n, device, stream)
+    parr = (ctypes.c_double * max(1, npct))(*pcts)
+    optr = None if outs is None else _out_ptrs(outs, n)
+    rc = L.wtp_prune_global_f32(desc, n, wid, int(level), parr, npct, flags, optr, ws.data_ptr(), ws.numel(),
+                                res.data_ptr(), ctypes.c_void_p(stream.cuda_stream))
+    if rc != N.WTP_OK:
+        raise_for(rc, tensors, wavelet)
+    return outs, res
+
+
+def prune_global(tensors, wavelet, level, pcts, outs=None, carry_level=True, thresholds_only=False):
+    """launch_global() + wait + decoded records: (outs, recs) with recs[k][t] the record of tensor t
+    at the pool's pcts[k]-th percentile (decode() of block k)."""
+    pcts = list(pcts)
+    outs, res = launch_global(tensors, wavelet, level, pcts, outs=outs, carry_level=carry_level,
+                              thresholds_only=thresholds_only)
     return outs, _decode_blocks(res, len(pcts), len(tensors), N.RESULT_BYTES, decode)
 
 
